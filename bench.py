@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched random-action rollout (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1 without a launcher: bench.py starts its own N ranks (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 ..., steppingstone_amd/launch.py), the way the reference's make_vec_envs forks its own
@@ -12,14 +12,17 @@ A "step" is one control step of every environment of the job: 4096 Walker3DStepp
 step = 4 physics substeps, contact solve, reward, termination, auto-reset, 60-float observation, all written to HBM.
   N = 1: the K timed steps run through ss_rollout_random's multi-step kernel (up to 1000 control steps
          per launch, state resident in LDS between steps, outputs and the HBM state copy written every step); the
-         one-launch-per-step path (what a policy-in-the-loop caller uses) is timed beside it as `per_step_launch`.
+         one-launch-per-step path (what a policy-in-the-loop caller uses) is timed beside it as `per_step_launch` (--full).
   N > 1: every rank owns 4096 envs (weak scaling) and every step's packed [4096,62] obs|rew|done block is all-gathered
          over RCCL (BASELINE configs[3]).  The same multi-step kernel runs here too: 32 control steps per launch, each
          step's block written to its own slot, ONE all-gather per 32-step chunk under the next chunk's kernel (same bytes
          per step on the wire, 32 x fewer collectives) -- so the N = 1 and N > 1 lines time the same kernel and their ratio
-         is the cost of the exchange, not of a different launch shape.  Side rows: `no_gather` (same K steps, no
+         is the cost of the exchange, not of a different launch shape.  Side rows (--full): `no_gather` (same K steps, no
          collective), `per_step_gather` (one launch + one all-gather per step: what a policy-in-the-loop caller pays).
-State is resident in HBM before the timed region.  Rank 0 prints ONE JSON line with `roofline` and `cpu_baseline`.
+State is resident in HBM before the timed region.  A plain run times exactly K steps in one region (after the clock-ramp launch
+and the W warm-up steps) and rank 0 prints ONE JSON line with `value` and `ms_per_step` of that region.  --full adds the repeated
+regions (median / min / max), `roofline`, the side rows, the exchange self-check, the Mike / capacity rows and `cpu_baseline` to the
+same line.  --dump-outputs DIR writes the last timed step's obs / rew / done (see dump_outputs).
 """
 import argparse
 import glob
@@ -234,6 +237,27 @@ def cpu_baseline(budget=24.0):
 
 
 # ------------------------------------------------------------------------------------------------ the bench
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, last):
+    """--dump-outputs: what the timed path returned for its last step -- (obs [N,60], rew [N], done [N]) of every env of the job
+    -- as DIR/obs.npy, DIR/rew.npy, DIR/done.npy in float32 (done as 0 / 1).  Above DUMP_MAX_BYTES in all, a fixed sample of
+    env rows (numpy default_rng(0), sorted) is written instead, and its row indices as DIR/sample_rows.npy (float64)."""
+    import numpy as np
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in zip(("obs", "rew", "done"), last)}
+    n = arrays["obs"].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        keep = int(n * DUMP_MAX_BYTES // (total + 8 * n))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_shape(W, K, spl, ms_per_step, prewarm=0):
     """The launches of the dominant kernel in this run (warm-up and timed) and the per-launch average a `rocprofv3 --stats`
     summary of the same command shows for it: the warm-up launch is shorter than the timed ones, so that average is not
@@ -305,8 +329,13 @@ def main():
     ap.add_argument("--env", default=ENV_ID)
     ap.add_argument("--curriculum", type=int, default=0)
     ap.add_argument("--steps-per-launch", type=int, default=0, help="N=1: control steps per kernel launch (0 = min(K, 1000); 1 = one launch per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the Mike / capacity side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timed regions (median / min / max), the roofline, the side rows, the exchange "
+                         "self-check, the Mike / capacity rows and the CPU baseline (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the obs / rew / done of their last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the Mike / capacity side measurements")
     ap.add_argument("--no-gather", action="store_true", help="N>1: time only the collective-free rollout")
     ap.add_argument("--per-step-exchange", action="store_true",
                     help="N>1: headline = one launch + one all-gather per step instead of 32-step chunks")
@@ -361,7 +390,6 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
 
     PHASE["name"] = "process group up"
-    devices = device_identity(torch, dist, dev, use_dist, world)
     n_local = args.envs_per_gpu
     if args.ppo:
         ppo_e2e(args, torch, dist, dev, rank, world, use_dist, n_local)
@@ -428,35 +456,84 @@ def main():
 
     if W:
         run(W, 0)
-    # The timed region: EXACTLY K steps between barrier + synchronize on both sides, max over ranks.  A region shorter than
-    # 50 ms (the driver runs --steps 20: 1 ms) is one noisy sample, so it is then repeated -- every repeat is again exactly K
-    # steps, continuing the rollout -- and the MEDIAN region is reported (min / max beside it).  Round 6: at least
-    # 9 regions AND until the regions add up to MIN_TIMED_S = 5 s of timed work (VERDICT asked for >= 0.1 s; the whole default run is ~20 s, 12 of them the CPU baseline; at most MAX_REPEATS), so that the driver's gpu_busy
-    # sampler sees the GPU working and the median rests on ~5000 regions instead of 9; `repeats` and `timed_region_s` say what was done.
-    # The stop rule uses the max-over-ranks times, so every rank runs the same number of regions.
+    # The headline: ONE timed region of EXACTLY K steps between barrier + synchronize on both sides, max over ranks, no
+    # instrumentation inside it.  `value` and `ms_per_step` come from this region alone.
+    t_next = W
+    last = []
+    el, _ = timed(lambda: last.append(run(K, t_next)), events=False)
+    elapsed = reduce_max(el)
+    t_next += K
+    if args.dump_outputs:
+        PHASE["name"] = "dump outputs"
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last[-1])
+    out = None
+    if rank == 0:
+        total_envs = n_local * world
+        value = total_envs * K / elapsed
+        steps_in_launch = spl if multi_step else (32 if chunked else 1)
+        out = {
+            "metric": "env-steps/sec (batched random-action rollout)",
+            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": 1e3 * elapsed / K,
+            "region_is": "one region of exactly %d steps between barrier + synchronize on both sides (max over ranks); value and "
+                         "ms_per_step are that region's" % K,
+            "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s, %d envs per MI355X, curriculum %d%s, on-device Philox U(-1,1) actions, auto-reset on"
+                                   % (args.env, n_local, args.curriculum, " (flat terrain)" if not args.curriculum else ""),
+                       "envs_total": total_envs,
+                       "parallelism": "env-shard x%d%s" % (world, "+allgather" if gather else ""),
+                       "ranks": world, "collective": ((("%s all_gather_into_tensor of [32,%%d,62] f32 per 32-step chunk, %%d ranks"
+                                                        if chunked else "%s all_gather_into_tensor of [%%d,62] f32 per step, %%d ranks")
+                                                       % (test_transport or "RCCL")) % (n_local, world)) if gather else None,
+                       "value_is": ("K-step launches of the rollout kernel (state resident in LDS between steps)" if multi_step else
+                                    "32-step launches + one all-gather per 32-step chunk" if (chunked and gather) else
+                                    "one launch%s per control step" % (" + one all-gather" if gather else "")),
+                       "steps_per_launch": steps_in_launch, "prewarm_steps": PREWARM,
+                       **({"test_transport": "%s, all ranks on ONE GPU: a functional run of the N > 1 path, not a measurement" % test_transport}
+                          if test_transport else {})},
+        }
+    if not args.full:
+        if rank == 0:
+            sys.stdout.write(json.dumps(out) + "\n")          # one write: nothing can land inside the line
+            sys.stdout.flush()
+        PHASE["name"] = "final barrier"
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if watchdog is not None:
+            watchdog.cancel()
+        return
+
+    # --full: everything beside the headline.  The headline region is repeated -- every repeat is again exactly K steps,
+    # continuing the rollout -- and the median / min / max over all regions (the headline region included) are reported beside
+    # `value`: at least 9 regions AND until the regions add up to MIN_TIMED_S = 5 s of timed work (at most MAX_REPEATS); a long
+    # region (>= 50 ms) needs no minimum count of repeats.  `repeats` and `timed_region_s` say what was done.  The stop rule uses
+    # the max-over-ranks times, so every rank runs the same number of regions.
     REPEAT_BELOW_S, MIN_REPEATS, MIN_TIMED_S, MAX_REPEATS = 0.05, 9, 5.0, 20000
     if test_transport:
         MIN_TIMED_S = 0.2          # a functional run of the N > 1 path (all ranks on one GPU): never a measurement
-    t_next = W
-    samples = []
+    PHASE["name"] = "repeated timed regions"
+    samples = [(elapsed, None)]
     # The two HIP events that measure the kernel time for the roofline are instrumentation INSIDE the timed region (two marker packets
-    # on the launch stream, ~9 us of a 20-step region's ~950): when a region is repeated they are recorded in every EVENTS_EVERY-th
-    # region only; `value` is the median over ALL regions (instrumented or not), `roofline.kernel_ms` the median over the instrumented.
+    # on the launch stream, ~9 us of a 20-step region's ~950): they are recorded in every EVENTS_EVERY-th repeat only (never in the
+    # headline region); `roofline.kernel_ms` is the median over the instrumented regions.
     EVENTS_EVERY = 4
-    for rep in range(MAX_REPEATS):
-        el, ev = timed(lambda: run(K, t_next), events=(rep % EVENTS_EVERY == 0))
+    for rep in range(1, MAX_REPEATS):
+        el, ev = timed(lambda: run(K, t_next), events=(rep % EVENTS_EVERY == 1))
         t_next += K
         samples.append((reduce_max(el), ev))
-        # a long region (>= 50 ms: the default 2000-step run) needs no minimum count of repeats, only the second of timed work
         if (rep + 1 >= MIN_REPEATS or samples[0][0] >= REPEAT_BELOW_S) and sum(s_[0] for s_ in samples) >= MIN_TIMED_S:
             break
     timed_region_s = sum(s_[0] for s_ in samples)
     order = sorted(range(len(samples)), key=lambda i: samples[i][0])
-    elapsed = samples[order[len(order) // 2]][0]
+    elapsed_median = samples[order[len(order) // 2]][0]
     evs = sorted(s_[1] for s_ in samples if s_[1] is not None)
     main_ev_ms = evs[len(evs) // 2]
     elapsed_min, elapsed_max = samples[order[0]][0], samples[order[-1]][0]
-    # self-proof of the exchange, straight after the headline run: every rank checksums its own block and each peer's block
+    devices = device_identity(torch, dist, dev, use_dist, world)
+    # self-proof of the exchange, straight after the timed regions: every rank checksums its own block and each peer's block
     # as received, the checksums are compared across ranks (ShardedVecEnv.verify_last_exchange)
     PHASE["name"] = "exchange verification / side rows"
     gather_verified = None
@@ -528,9 +605,6 @@ def main():
         side[k]["value"] = n_local * world / (side[k]["ms_per_step"] * 1e-3)
 
     if rank == 0:
-        total_envs = n_local * world
-        value = total_envs * K / elapsed
-        steps_in_launch = spl if multi_step else (32 if chunked else 1)
         # roofline.achieved uses SURVEY 8(d)'s per-unit figure recomputed for this layout (905 B per env-step: the state
         # round trip a step() implies) x the env-steps one launch processes.  The K-step kernel really moves less (the 376 B
         # of state are read once per launch): that figure is reported next to it, as is the PMC-measured traffic.
@@ -553,28 +627,11 @@ def main():
             kernel = ("ss::rollout_kernel_helped<%s,%d>" % (model, helpers)) if helpers else "ss::rollout_kernel<%s>" % model
         else:
             kernel = ("ss::step_kernel_helped<%s,true,%d>" % (model, helpers)) if helpers else "ss::step_kernel<%s,true>" % model
-        out = {
-            "metric": "env-steps/sec (batched random-action rollout)",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": 1e3 * elapsed / K, "repeats": len(samples), "timed_region_s": timed_region_s,
-            "hip_events_in_regions": len(evs),
-            "region_is": "exactly %d steps between barrier + synchronize on both sides; value = median of `repeats` such regions" % K,
-            "ms_per_step_min": 1e3 * elapsed_min / K,
-            "ms_per_step_max": 1e3 * elapsed_max / K, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s, %d envs per MI355X, curriculum %d%s, on-device Philox U(-1,1) actions, auto-reset on"
-                                   % (args.env, n_local, args.curriculum, " (flat terrain)" if not args.curriculum else ""),
-                       "envs_total": total_envs,
-                       "parallelism": "env-shard x%d%s" % (world, "+allgather" if gather else ""),
-                       "ranks": world, "collective": ((("%s all_gather_into_tensor of [32,%%d,62] f32 per 32-step chunk, %%d ranks"
-                                                        if chunked else "%s all_gather_into_tensor of [%%d,62] f32 per step, %%d ranks")
-                                                       % (test_transport or "RCCL")) % (n_local, world)) if gather else None,
-                       "value_is": ("K-step launches of the rollout kernel (state resident in LDS between steps)" if multi_step else
-                                    "32-step launches + one all-gather per 32-step chunk" if (chunked and gather) else
-                                    "one launch%s per control step" % (" + one all-gather" if gather else "")),
-                       "steps_per_launch": steps_in_launch, "prewarm_steps": PREWARM,
-                       **({"test_transport": "%s, all ranks on ONE GPU: a functional run of the N > 1 path, not a measurement" % test_transport}
-                          if test_transport else {})},
+        out.update({
+            "repeats": len(samples), "timed_region_s": timed_region_s, "hip_events_in_regions": len(evs),
+            "repeats_are": "the headline region and %d more regions of exactly %d steps each, continuing the rollout" % (len(samples) - 1, K),
+            "ms_per_step_median": 1e3 * elapsed_median / K,
+            "ms_per_step_min": 1e3 * elapsed_min / K, "ms_per_step_max": 1e3 * elapsed_max / K,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "B/launch",
                          "traffic_model": tinfo,
@@ -588,7 +645,7 @@ def main():
                                                         "note": "the same kernel time priced at SURVEY 8(d)'s 905 B per env-step (state read AND "
                                                                 "written every step): what a one-launch-per-step caller's traffic would be"},
                          "note": pmc_note(pmc), "note_source": pmc_src},
-        }
+        })
         out.update(side)
         # the figure a policy-in-the-loop caller gets (one launch -- and at N > 1 one all-gather -- per control step), with the
         # same prominence as `value` (the reference's loop consumes every step: playground/train.py:373)

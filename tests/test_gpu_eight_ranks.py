@@ -85,7 +85,7 @@ def test_bench_gpus_8_runs_the_configs3_workload_end_to_end_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "64", "--warmup", "32",
-                          "--envs-per-gpu", "4096", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--envs-per-gpu", "4096", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rows = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(rows) == 1                                             # rank 0 only

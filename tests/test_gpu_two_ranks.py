@@ -115,7 +115,7 @@ def test_bench_two_rank_path_runs_end_to_end_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "64", "--warmup", "32",
-                          "--envs-per-gpu", "1024"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          "--envs-per-gpu", "1024", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rows = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(rows) == 1                                             # rank 0 only

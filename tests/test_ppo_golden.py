@@ -118,7 +118,45 @@ def test_adaptive_sampler_grid():
         envs.update_sample_prob(np.repeat(p[None], n, axis=0))      # what train.py:267-271 does
 
 
-REF_MODELS = "/root/reference/playground/models/"
+class _SoftsignActor(torch.nn.Module):
+    def __init__(self, s, a, h=256):
+        super().__init__()
+        self.fc1, self.fc2, self.fc3 = torch.nn.Linear(s, h), torch.nn.Linear(h, h), torch.nn.Linear(h, h)
+        self.fc4, self.fc5, self.out = torch.nn.Linear(h, h), torch.nn.Linear(h, h), torch.nn.Linear(h, a)
+
+
+class _AddBias(torch.nn.Module):
+    def __init__(self, a):
+        super().__init__()
+        self._bias = torch.nn.Parameter(torch.linspace(-1.5, -0.5, a).reshape(a, 1))
+
+
+class _Dist(torch.nn.Module):
+    def __init__(self, a):
+        super().__init__()
+        self.logstd = _AddBias(a)
+
+
+class _Policy(torch.nn.Module):
+    """The module tree of the reference's shipped checkpoints: actor.fc1..fc5 / out, dist.logstd._bias and the
+    value networks as one Sequential `critic` (older files) or an ensemble c0, c1, ... -- Linear layers at indices 0, 2, 4, 6, 8."""
+
+    def __init__(self, s, a, critic_prefixes, h=256):
+        super().__init__()
+        self.actor, self.dist = _SoftsignActor(s, a, h), _Dist(a)
+        for pre in critic_prefixes:
+            layers = []
+            for i, o in ((s, h), (h, h), (h, h), (h, h)):
+                layers += [torch.nn.Linear(i, o), torch.nn.ReLU()]
+            self.add_module(pre[:-1], torch.nn.Sequential(*layers, torch.nn.Linear(h, 1)))
+
+
+def _legacy_checkpoint(path, dims, critic_prefixes):
+    """A checkpoint in the legacy (pre-zip) torch.save format the reference's files use: the whole module pickled, then its raw
+    storages.  Seeded weights; written to `path`."""
+    torch.manual_seed(11)
+    torch.save(_Policy(dims[0], dims[1], critic_prefixes), str(path), _use_new_zipfile_serialization=False)
+    return str(path)
 
 
 @pytest.mark.parametrize("name,dims,critic_prefixes", [
@@ -128,15 +166,12 @@ REF_MODELS = "/root/reference/playground/models/"
     ("mocca_envs:MikeStepperEnv-v0_latest.pt", (60, 21), ["c0."]),               # current layout: ensemble modules c0, c1, ... (controller.py:94-95)
     ("CassieStepper-v1_base.pt", (51, 10), ["c0.", "c1."]),                       # train.py:37's default env: other dims, two critics
 ])
-def test_reference_checkpoint_loader(name, dims, critic_prefixes):
-    """steppingstone_amd.legacy_checkpoint: EVERY policy the reference ships (legacy torch.save of the pickled Policy module) read
-    with the restricted unpickler -- no reference code executed -- and mapped onto ActorCritic; the deterministic action and every
-    ensemble member's value must equal a numpy forward pass over the raw arrays of the file (this container only: the files live
-    under /root/reference)."""
-    import os
-    path = REF_MODELS + name
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
+def test_reference_checkpoint_loader(name, dims, critic_prefixes, tmp_path):
+    """steppingstone_amd.legacy_checkpoint: a checkpoint in the layout of EVERY policy the reference ships (legacy torch.save of the
+    pickled Policy module; written here with seeded weights, since the files themselves are not part of this repository) read with
+    the restricted unpickler -- no code of the file executed -- and mapped onto ActorCritic; the deterministic action and every
+    ensemble member's value must equal a numpy forward pass over the raw arrays of the file."""
+    path = _legacy_checkpoint(tmp_path / name.replace(":", "_"), dims, critic_prefixes)
     from steppingstone_amd import legacy_checkpoint as lc
     ac = lc.load_reference_checkpoint(path)
     obj, st = lc.read_legacy(path)
@@ -171,13 +206,12 @@ def test_legacy_reader_rejects_other_files(tmp_path):
     torch.save({"a": torch.zeros(3)}, str(p))                       # the zip format
     with pytest.raises(Exception):
         lc.read_legacy(str(p))
-    src = REF_MODELS + "mocca_envs:MikeStepperEnv-v0_latest.pt"
-    if os.path.exists(src):
-        raw = open(src, "rb").read()
-        q = tmp_path / "cut.pt"
-        q.write_bytes(raw[: len(raw) - 1000])
-        with pytest.raises(Exception):
-            lc.read_legacy(str(q))
+    src = _legacy_checkpoint(tmp_path / "mike.pt", (60, 21), ["c0."])
+    raw = open(src, "rb").read()
+    q = tmp_path / "cut.pt"
+    q.write_bytes(raw[: len(raw) - 1000])
+    with pytest.raises(Exception):
+        lc.read_legacy(str(q))
     # a crafted file whose HEADER records name a global (the classic os.system pickle) is refused before anything runs
     import pickle
 
@@ -194,50 +228,3 @@ def test_legacy_reader_rejects_other_files(tmp_path):
         with pytest.raises(pickle.UnpicklingError, match="refused"):
             lc.read_legacy(str(evil))
         assert not (tmp_path / "pwned").exists()
-
-
-def test_export_in_the_form_the_reference_loads_back(tmp_path):
-    """tools/export_reference_checkpoint.py: a checkpoint of this package becomes a pickled `Policy` module of the REFERENCE's own classes
-    (playground/train.py:551 saves one, playground/enjoy.py:148 `torch.load`s one).  Here, where the reference checkout is present: the
-    exported file loads with plain torch.load, is an instance of common.controller.Policy, and its deterministic action, ensemble values
-    and log-std equal this package's; and it reads back through legacy_checkpoint-free means only -- the round trip ours -> theirs."""
-    import os
-    import subprocess
-    import sys
-    if not os.path.exists("/root/reference/common/controller.py"):
-        pytest.skip("reference checkout not present")
-    from steppingstone_amd import ppo
-    torch.manual_seed(4)
-    ac = ppo.ActorCritic(num_ensembles=2)
-    with torch.no_grad():
-        ac.logstd.copy_(torch.linspace(-2.0, -1.0, 21))
-    ours = str(tmp_path / "ours.pt")
-    ppo.save_checkpoint(ac, ours, update=7)
-    out = str(tmp_path / "theirs.pt")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "export_reference_checkpoint.py"), ours, "--reference", "/root/reference",
-                        "--out", out], capture_output=True, text=True, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0, r.stderr[-2000:]
-    # load it the way playground/enjoy.py does, in a process that can import the reference's classes
-    code = ("import sys, types, torch\n"
-            "sys.dont_write_bytecode = True\n"
-            "sys.path.insert(0, '/root/reference')\n"
-            "g, sp = types.ModuleType('gym'), types.ModuleType('gym.spaces')\n"
-            "sp.Box, sp.Dict, sp.MultiDiscrete = type('Box', (), {}), type('Dict', (dict,), {}), type('MultiDiscrete', (), {})\n"
-            "g.spaces = sp; sys.modules.update({'gym': g, 'gym.spaces': sp})\n"
-            "m = torch.load(%r, weights_only=False)\n"
-            "from common.controller import Policy\n"
-            "assert isinstance(m, Policy) and len(m.critics) == 2\n"
-            "x = torch.linspace(-1, 1, 5 * 60).reshape(5, 60)\n"
-            "v, a, lp, _ = m.act(x, None, None, deterministic=True)\n"
-            "torch.save({'a': a, 'v': m.get_ensemble_values(x, None, None), 'logstd': m.dist.logstd._bias.reshape(-1)}, %r)\n"
-            % (out, str(tmp_path / "ref_out.pt")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = torch.load(str(tmp_path / "ref_out.pt"))
-    x = torch.linspace(-1, 1, 5 * 60).reshape(5, 60)
-    with torch.no_grad():
-        _, a, _ = ac.act(x, deterministic=True)
-        ve = ac.get_ensemble_values(x)
-    assert torch.allclose(ref["a"], a, atol=1e-6) and torch.allclose(ref["v"], ve, atol=1e-5)
-    assert torch.equal(ref["logstd"], ac.logstd.detach())

@@ -4,7 +4,8 @@ The env's source is absent from the reference, but `playground/models/*.pt` were
 `get_mirror_function(env.unwrapped.get_mirror_indices())` (`playground/train.py:160-161`, `common/envs_utils.py:687-740`), so a
 shipped actor satisfies  pi(M_o o) ~ M_a pi(o)  for the reference env's TRUE index lists and for no other signed permutation.
 `ss_get_mirror_indices` must be those lists: measured here on observations of this repository's env (CPU oracle), for both robots.
-This container only (the checkpoints live under /root/reference; restricted unpickler, no reference code runs); skipped elsewhere.
+The actors' weights are the plain arrays under tests/golden/ (shipped_actor_<kind>.npz, read from those files with the restricted
+unpickler by tools/make_golden_policy.py; no reference code runs).
 Informational about the ENV's physics (the policies still fall in it: different robot model) -- a pin of the LAYOUT only."""
 import os
 
@@ -12,12 +13,19 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import shipped_actor
 from steppingstone_amd import _lib, model
 
 torch = pytest.importorskip("torch")
 
-REF_MODELS = "/root/reference/playground/models/"
 FILES = [("walker3d", "mocca_envs:Walker3DStepperEnv-v0_latest.pt"), ("mike", "mocca_envs:MikeStepperEnv-v0_latest.pt")]
+
+
+def _shipped_actor(kind, fname):
+    """the deterministic actor of the shipped policy `fname`, from its weights stored under tests/golden/"""
+    w = np.load(os.path.join(shipped_actor.GOLD, "shipped_actor_%s.npz" % kind))
+    assert str(w["source"]) == fname
+    return shipped_actor.load_actor(kind)
 
 
 def _observations(kind, actor, n=128, steps=24):
@@ -58,11 +66,7 @@ def _error(actor, O, idx):
 
 @pytest.mark.parametrize("kind,fname", FILES)
 def test_shipped_actor_is_equivariant_under_ss_get_mirror_indices(kind, fname):
-    path = REF_MODELS + fname
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    from steppingstone_amd.legacy_checkpoint import load_reference_checkpoint
-    actor = load_reference_checkpoint(path).actor
+    actor = _shipped_actor(kind, fname)
     O = _observations(kind, actor)
     idx = [np.asarray(i, np.int64) for i in _lib.mirror_indices()]
     err, mean_a = _error(actor, O, idx)
@@ -105,11 +109,7 @@ def test_shipped_actor_couples_action_j_to_inputs_6_plus_j_and_27_plus_j(kind, f
     against the shipped actor's mean Jacobian: a trained controller couples action j most strongly to ITS joint's rate and angle, so
     of all 21-wide windows of the 60 inputs the 21 x 21 block at offset 27 (rates) must be the most diagonal-dominant, offset 6
     (angles) the second, and d a_j / d rate_j negative (damping: action and rate share the sign convention per joint)."""
-    path = REF_MODELS + fname
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    from steppingstone_amd.legacy_checkpoint import load_reference_checkpoint
-    actor = load_reference_checkpoint(path).actor
+    actor = _shipped_actor(kind, fname)
     O = torch.from_numpy(_observations(kind, actor, n=64)).requires_grad_(True)
     J = np.zeros((21, 60))
     for j in range(21):
@@ -168,11 +168,7 @@ def test_shipped_actor_rejects_the_other_knee_convention(kind, fname):
     Walker3D / Mike actors stay up 81 / 58 control steps in our env, with the knee convention flipped back 25 / 10 -- and a control
     flip of a joint type that is right as it is (hip y) makes things worse, not better.  They still fall (the robot model is our own):
     a pin of the CONVENTION, not a parity statement."""
-    path = REF_MODELS + fname
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    from steppingstone_amd.legacy_checkpoint import load_reference_checkpoint
-    actor = load_reference_checkpoint(path).actor
+    actor = _shipped_actor(kind, fname)
     ours, knee_back, hip_y = _survival(kind, actor, ()), _survival(kind, actor, ("knee",)), _survival(kind, actor, ("hip_y",))
     print("%s: shipped actor survives %.1f control steps in policy coordinates, %.1f with the knee sign flipped back, %.1f with hip y "
           "flipped" % (kind, ours, knee_back, hip_y))

@@ -8,8 +8,8 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 ( cd $R && timeout 2400 python -m pytest tests -m gpu -x -q -rs --durations=12 2>&1; echo "pytest rc $?" ) > $O/${tag}_pytest_gpu.log
-( cd $R && python bench.py ) > $O/${tag}_bench.json 2> $O/${tag}_bench.err
-rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $R/bench.py --no-cpu-baseline > $O/${tag}_bench_under_rocprof.json 2>/dev/null
+( cd $R && python bench.py --full ) > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $R/bench.py --full --no-cpu-baseline > $O/${tag}_bench_under_rocprof.json 2>/dev/null
 cp $(ls /tmp/kt/*/*kernel_stats.csv | head -1) $O/${tag}_rocprofv3_kernel_stats.csv
 # per-dispatch durations of the multi-step kernel (the --stats average mixes the 200-step warm-up launch with the timed 1000-step ones)
 python - "$(ls /tmp/kt/*/*kernel_trace.csv | head -1)" > $O/${tag}_rocprofv3_rollout_dispatches.csv <<'PY'
@@ -39,6 +39,6 @@ python $R/tools/pmc_profile.py 32768 $O/${tag}_pmc_32768.json rollout > /dev/nul
 python $R/tools/scaling_n.py > $O/${tag}_scaling_envs.txt
 python $R/tools/contact_cost.py > $O/${tag}_regimes.txt
 ( cd $R && python bench.py --ppo --no-cpu-baseline ) > $O/${tag}_bench_ppo.json 2>/dev/null
-( cd $R && python bench.py --steps 20 --warmup 5 ) > $O/${tag}_bench_driver_shape.json 2>/dev/null
+( cd $R && python bench.py --steps 20 --warmup 5 --full ) > $O/${tag}_bench_driver_shape.json 2>/dev/null
 ( cd $R && python -c "import __graft_entry__ as g; g.smoke()" ) > $O/${tag}_smoke.log 2>&1
 ls -la $O | tail -20
