@@ -35,7 +35,9 @@ extern "C" {
 #define SS_STATE_DIM 186  /* packed per-env state of ss_get_state / ss_set_state */
 #define SS_INFO_WORDS 6    /* 32-bit words of ss_info */
 #define SS_ABI_VERSION 4   /* ss_version(): 2 -> 3 added ss_info.ep_ret_lo and state word 185 (round 3); 3 -> 4 (round 4) changed a
-                            * MEANING, no layout: actions and observations carry POLICY coordinates, see "Joint conventions" */
+                            * MEANING, no layout: actions and observations carry POLICY coordinates, see "Joint conventions".
+                            * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) were ADDED under
+                            * version 4: no existing layout or meaning changed, so a version-4 binding keeps working. */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -171,6 +173,33 @@ int32_t ss_num_envs(const ss_env* env);
  * steps_per_launch into ss_rollout_random's argument list, version 3 grew ss_info to 6 words and the packed state to 186,
  * version 4 changed the sign convention of the left limbs' x / z joints and of the knees in actions and observations (same layouts). */
 int ss_version(void);
+
+/* Rendering (docs/RENDER.md is the specification).  Both calls only READ the environment state, are ordered on `stream`, never
+ * synchronise the host and allocate nothing: they can be captured into a hipGraph next to the steps.
+ * ss_camera: mode SS_CAM_TRACK (default) -- target = torso position + target[], eye = target + eye[] (world-frame offsets);
+ * SS_CAM_CHASE -- the same with both offsets turned by the torso's yaw (per-env pixel observations); SS_CAM_FIXED -- eye[] and
+ * target[] in world coordinates.  Vertical field of view fov_y_deg in (0, 180); far_m > 0 (depth of the background, and no hit at or
+ * beyond it counts); flags bit 0: hard shadows.  ss_camera_default fills the TRACK camera that frames a reset robot and its next stone. */
+typedef enum { SS_CAM_TRACK = 0, SS_CAM_CHASE = 1, SS_CAM_FIXED = 2 } ss_camera_mode;
+#define SS_CAM_SHADOWS 1
+typedef struct {
+  int32_t mode;
+  float eye[3];
+  float target[3];
+  float fov_y_deg;
+  float far_m;
+  int32_t flags;
+} ss_camera;
+int ss_camera_default(ss_camera* cam);
+/* World pose of all 22 bodies (torso = body 0, body j+1 = child link of joint j): out [N, 22, 12] f32 = position | R row-major,
+ * the frame convention of steppingstone_amd/model.py fk().  DEVICE pointer, 16-byte aligned. */
+int ss_body_poses(ss_env* env, float* out, void* stream);
+/* Frames of the m envs listed in env_ids (DEVICE [m] int32): rgb [m,H,W,3] u8, depth [m,H,W] f32 (z-depth; background = far_m),
+ * seg [m,H,W] u8 (0 background, 1 + body, 23 / 24 / 25 the stones n-1 / n / n+1).  Any output may be NULL, not all three; rgb and seg
+ * must be 4-byte aligned.  width and height: multiples of 4 in 4..2048; m >= 1.  Bad arguments return SS_ERR_INVALID and launch
+ * nothing.  An env id outside [0, N) lives on the device and is not checked here: that env is drawn as background. */
+int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int32_t height, const ss_camera* cam, uint8_t* rgb,
+              float* depth, uint8_t* seg, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

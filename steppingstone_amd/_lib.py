@@ -20,7 +20,17 @@ SYMBOLS = [
     "ss_version", "ss_set_sample_prob_device", "ss_debug_calib_copy", "ss_debug_phase_cycles",
     "ss_peer_alloc", "ss_peer_free", "ss_peer_ipc_handle", "ss_peer_ipc_open", "ss_peer_ipc_close", "ss_peer_connect",
     "ss_step_packed_peers", "ss_peer_wait", "ss_peer_error", "ss_rollout_random_packed", "ss_debug_set_id_mask",
+    "ss_camera_default", "ss_body_poses", "ss_render",
 ]
+NUM_BODIES = 22           # torso + 21 links: ss_body_poses rows per env
+CAM_TRACK, CAM_CHASE, CAM_FIXED = 0, 1, 2     # ss_camera.mode
+CAM_SHADOWS = 1                                # ss_camera.flags bit 0
+
+
+class Camera(C.Structure):
+    """ss_camera (include/steppingstone.h, docs/RENDER.md 1)."""
+    _fields_ = [("mode", C.c_int32), ("eye", C.c_float * 3), ("target", C.c_float * 3), ("fov_y_deg", C.c_float),
+                ("far_m", C.c_float), ("flags", C.c_int32)]
 
 
 class SteppingStoneError(RuntimeError):
@@ -78,6 +88,9 @@ def load():
     lib.ss_num_envs.argtypes = [vp]
     lib.ss_num_envs.restype = i32
     lib.ss_version.restype = C.c_int
+    lib.ss_camera_default.argtypes = [vp]
+    lib.ss_body_poses.argtypes = [vp, vp, vp]
+    lib.ss_render.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     if lib.ss_version() != ABI_VERSION:
         # the argument lists and struct sizes changed between versions (2: steps_per_launch in ss_rollout_random; 3: ss_info has 6
         # words, the packed state 186): a stale library would be called with the wrong layout and no error
@@ -91,6 +104,13 @@ def check(rc):
     if rc != 0:
         msg = load().ss_last_error()
         raise SteppingStoneError("libsteppingstone error %d: %s" % (rc, msg.decode() if msg else "?"))
+
+
+def default_camera():
+    """ss_camera_default(): the TRACK camera that frames a reset robot and its next stone."""
+    cam = Camera()
+    check(load().ss_camera_default(C.byref(cam)))
+    return cam
 
 
 def mirror_indices(kind=WALKER3D):

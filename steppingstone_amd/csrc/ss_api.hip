@@ -13,6 +13,12 @@
 // compiled in ss_rollout3.hip (its own scheduling strategy, see there)
 extern template __global__ void ss::rollout_kernel_helped<ss::ModelWalker3D, 3>(ss::Params, ss::StepIO);
 extern template __global__ void ss::rollout_kernel_helped<ss::ModelMike, 3>(ss::Params, ss::StepIO);
+// compiled in ss_render.hip (the render kernels, docs/RENDER.md)
+namespace ss {
+hipError_t launch_render(const Params& P, int kind, const int32_t* env_ids, int m, int W, int H, const ss_camera& cam,
+                         unsigned char* rgb, float* depth, unsigned char* seg, hipStream_t st);
+hipError_t launch_body_poses(const Params& P, int kind, float* out, hipStream_t st);
+}  // namespace ss
 
 
 namespace {
@@ -550,6 +556,40 @@ int ss_get_obs(ss_env* env, float* obs, void* stream) {
   else
     hipLaunchKernelGGL((ss::obs_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, (hipStream_t)stream, env->P, obs);
   SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+int ss_camera_default(ss_camera* cam) {
+  if (!cam) return fail(SS_ERR_INVALID, "null argument");
+  // docs/RENDER.md 1: a three-quarter view from the robot's right, aimed ahead of the torso and below it, so that a reset robot
+  // (torso 1.0-1.2 m up) and its next stone 0.75 m ahead both fill the frame
+  *cam = ss_camera{SS_CAM_TRACK, {-0.9f, -2.3f, 0.45f}, {0.4f, 0.f, -0.5f}, 45.f, 20.f, SS_CAM_SHADOWS};
+  return SS_OK;
+}
+
+int ss_body_poses(ss_env* env, float* out, void* stream) {
+  if (!env || !out) return fail(SS_ERR_INVALID, "null argument");
+  if ((uintptr_t)out & 15) return fail(SS_ERR_INVALID, "ss_body_poses: out must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_body_poses(env->P, env->kind, out, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int32_t height, const ss_camera* cam, uint8_t* rgb,
+              float* depth, uint8_t* seg, void* stream) {
+  if (!env || !env_ids || !cam) return fail(SS_ERR_INVALID, "null argument");
+  if (m < 1) return fail(SS_ERR_INVALID, "ss_render: m must be >= 1");
+  if (width < 4 || height < 4 || width > 2048 || height > 2048 || width % 4 || height % 4)
+    return fail(SS_ERR_INVALID, "ss_render: width and height must be multiples of 4 in 4..2048");
+  if (!rgb && !depth && !seg) return fail(SS_ERR_INVALID, "ss_render: rgb, depth and seg are all NULL");
+  if (cam->mode != SS_CAM_TRACK && cam->mode != SS_CAM_CHASE && cam->mode != SS_CAM_FIXED)
+    return fail(SS_ERR_INVALID, "ss_render: camera mode must be SS_CAM_TRACK, SS_CAM_CHASE or SS_CAM_FIXED");
+  if (!(cam->fov_y_deg > 0.f && cam->fov_y_deg < 180.f) || !(cam->far_m > 0.f && cam->far_m < 3.0e38f))
+    return fail(SS_ERR_INVALID, "ss_render: fov_y_deg must lie in (0, 180) and far_m be positive and finite");
+  if (((uintptr_t)rgb & 3) || ((uintptr_t)seg & 3) || ((uintptr_t)depth & 3))
+    return fail(SS_ERR_INVALID, "ss_render: rgb, depth and seg must be 4-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_render(env->P, env->kind, env_ids, m, width, height, *cam, rgb, depth, seg, (hipStream_t)stream));
   return SS_OK;
 }
 

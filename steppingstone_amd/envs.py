@@ -151,6 +151,35 @@ class HipBackend:
     def get_obs(self, obs):
         _lib.check(self.lib.ss_get_obs(self.h, _ptr(obs), _stream(self.device)))
 
+    def body_poses(self, out):
+        _lib.check(self.lib.ss_body_poses(self.h, _ptr(out), _stream(self.device)))
+
+    def render(self, env_ids, width, height, camera, rgb, depth, seg):
+        """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_render(self.h, _ptr(env_ids), int(env_ids.numel()), int(width), int(height), C.byref(camera),
+                                      opt(rgb), opt(depth), opt(seg), _stream(self.device)))
+
+
+CAMERA_MODES = {"track": _lib.CAM_TRACK, "chase": _lib.CAM_CHASE, "fixed": _lib.CAM_FIXED}
+
+
+def make_camera(mode="track", eye=None, target=None, fov_y_deg=None, far_m=None, shadows=True):
+    """An ss_camera (docs/RENDER.md 1): mode "track" (default) / "chase" take eye and target as offsets (target from the torso, eye from
+    the target; "chase" turns both by the torso's yaw), "fixed" takes them in world coordinates.  Unset fields keep the defaults."""
+    cam = _lib.default_camera()
+    cam.mode = CAMERA_MODES[mode] if isinstance(mode, str) else int(mode)
+    if eye is not None:
+        cam.eye[:] = [float(x) for x in eye]
+    if target is not None:
+        cam.target[:] = [float(x) for x in target]
+    if fov_y_deg is not None:
+        cam.fov_y_deg = float(fov_y_deg)
+    if far_m is not None:
+        cam.far_m = float(far_m)
+    cam.flags = _lib.CAM_SHADOWS if shadows else 0
+    return cam
+
 
 class SteppingStoneVecEnv:
     """N stepping-stone environments advanced by one HIP kernel launch per step.
@@ -297,11 +326,47 @@ class SteppingStoneVecEnv:
         self.backend.close()
         self.closed = True
 
-    def render(self, mode="human"):
-        raise NotImplementedError("rendering is out of scope for the GPU env")
+    def render(self, mode="rgb_array", env_ids=None, width=256, height=192, camera=None, depth=False, seg=False, rgb=True):
+        """Frames of the envs `env_ids` (default: all) drawn on the GPU (docs/RENDER.md): rgb [M,H,W,3] uint8, depth [M,H,W] float32
+        (z-depth, background = far), seg [M,H,W] uint8 (0 background, 1 + body, 23 / 24 / 25 stones n-1 / n / n+1).  Returns the one
+        output requested, else a tuple in the order rgb, depth, seg; tensors on the env's device, numpy arrays in numpy mode.
+        camera: None (the default TRACK camera), an ss_camera (make_camera) or a dict of make_camera's arguments.  There is no window:
+        mode="human" raises NotImplementedError."""
+        if mode != "rgb_array":
+            raise NotImplementedError("render(mode=%r): only mode='rgb_array' is supported (there is no GUI)" % (mode,))
+        if not hasattr(self.backend, "render"):
+            raise NotImplementedError("this backend does not render")
+        if env_ids is None:
+            ids = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        else:
+            ids = torch.as_tensor(env_ids).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        if camera is None:
+            camera = make_camera()
+        elif isinstance(camera, dict):
+            camera = make_camera(**camera)
+        m = int(ids.numel())
+        out_rgb = torch.empty((m, height, width, 3), dtype=torch.uint8, device=self.device) if rgb else None
+        out_depth = torch.empty((m, height, width), dtype=torch.float32, device=self.device) if depth else None
+        out_seg = torch.empty((m, height, width), dtype=torch.uint8, device=self.device) if seg else None
+        self.backend.render(ids, width, height, camera, out_rgb, out_depth, out_seg)
+        outs = [t for t in (out_rgb, out_depth, out_seg) if t is not None]
+        if self.return_numpy:
+            outs = [t.cpu().numpy() for t in outs]
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
-    def get_images(self):
-        raise NotImplementedError("rendering is out of scope for the GPU env")
+    def get_images(self, width=256, height=192):
+        """VecEnv.get_images: one (H, W, 3) uint8 numpy frame per env (default camera)."""
+        if not hasattr(self.backend, "render"):
+            raise NotImplementedError("this backend does not render")
+        frames = self.render("rgb_array", width=width, height=height)
+        frames = frames.cpu().numpy() if torch.is_tensor(frames) else frames
+        return list(frames)
+
+    def body_poses(self):
+        """World pose of every body of every env, [N, 22, 12] float32: position | R row-major (model.fk's frames)."""
+        out = torch.empty((self.num_envs, _lib.NUM_BODIES, 12), dtype=torch.float32, device=self.device)
+        self.backend.body_poses(out)
+        return out.cpu().numpy() if self.return_numpy else out
 
     @property
     def unwrapped(self):
@@ -442,9 +507,8 @@ class SteppingStoneEnv:
     playground/train.py:96,129-131,231-247 and playground/enjoy.py:101-102,231-235 use these members)."""
 
     def __init__(self, env_id, seed=0, device=None, render=False, backend_factory=None):
-        if render:
-            raise NotImplementedError("rendering is out of scope for the GPU env")
         self._env_id = env_id
+        self.render_mode = "rgb_array" if render else None     # there is no window: render=True means frames on request
         self._device = device
         self._backend_factory = backend_factory
         self._make(seed)
@@ -486,8 +550,9 @@ class SteppingStoneEnv:
         info = dict(infos[0])
         return obs[0], float(rew[0]), bool(done[0]), info
 
-    def render(self, mode="human"):
-        raise NotImplementedError("rendering is out of scope for the GPU env")
+    def render(self, mode="rgb_array", width=256, height=192, camera=None):
+        """One (H, W, 3) uint8 frame of the env (SteppingStoneVecEnv.render); mode="human" raises NotImplementedError."""
+        return self.vec.render(mode, width=width, height=height, camera=camera)[0]
 
     def close(self):
         self.vec.close()

@@ -188,26 +188,29 @@ def _humanoid(P):
         DENSITY = dens0
 
 
-def _humanoid_at_density(P):
-    scale_leg, scale_arm, torso_w, mass_scale, z_extra_head = P["leg_scale"], P["arm_scale"], P["torso_w"], P["mass_scale"], P["head_extra"]
-    g = {}          # body -> list of geoms
+def _layout(P):
+    """The robot's shapes: body -> [(type, args)] with type "capsule" (p0, p1, r), "sphere" (c, r) or "box" (c, half), in the link
+    frame; body -> mass group; joint offsets r.  What is simulated (their masses and inertias, _humanoid_at_density) and what is drawn
+    (visual_geoms, docs/RENDER.md) are the same shapes."""
+    scale_leg, scale_arm, torso_w, z_extra_head = P["leg_scale"], P["arm_scale"], P["torso_w"], P["head_extra"]
+    g = {}          # body -> list of shapes
     grp = {}        # body -> mass group
     r = np.zeros((NJ, 3))
     # ---- torso (body 0): chest capsule across y, head, upper waist
     g[0] = [
-        _capsule([0, -torso_w, 0], [0, torso_w, 0], 0.07),
-        _sphere([0, 0, 0.19 + z_extra_head], 0.09 + z_extra_head * 0.5),
-        _capsule([-0.01, -0.06, -0.12], [-0.01, 0.06, -0.12], 0.06),
+        ("capsule", [0, -torso_w, 0], [0, torso_w, 0], 0.07),
+        ("sphere", [0, 0, 0.19 + z_extra_head], 0.09 + z_extra_head * 0.5),
+        ("capsule", [-0.01, -0.06, -0.12], [-0.01, 0.06, -0.12], 0.06),
     ]
     grp[0] = "torso"
     # ---- spine: abdomen_z (massless) -> abdomen_y (lwaist) -> abdomen_x (pelvis)
     r[0] = [P["spine_r0"][0], 0, P["spine_r0"][1]]
     g[1] = []
     r[1] = [0, 0, 0]
-    g[2] = [_capsule([0, -0.06, -0.065], [0, 0.06, -0.065], 0.06)]
+    g[2] = [("capsule", [0, -0.06, -0.065], [0, 0.06, -0.065], 0.06)]
     grp[2] = "lwaist"
     r[2] = [0, 0, P["spine_r2"]]
-    g[3] = [_capsule([-0.02, -0.07, -0.10], [-0.02, 0.07, -0.10], 0.09)]
+    g[3] = [("capsule", [-0.02, -0.07, -0.10], [-0.02, 0.07, -0.10], 0.09)]
     grp[3] = "pelvis"
     # ---- legs
     thigh = P["thigh"] * scale_leg
@@ -225,13 +228,13 @@ def _humanoid_at_density(P):
         r[j0 + 1] = [0, 0, 0]                 # hip_z co-located
         g[j0 + 2] = []
         r[j0 + 2] = [0, 0, 0]                 # hip_y co-located -> thigh
-        g[j0 + 3] = [_capsule([0, 0, 0], [0, 0, -thigh], P["thigh_radius"])]
+        g[j0 + 3] = [("capsule", [0, 0, 0], [0, 0, -thigh], P["thigh_radius"])]
         grp[j0 + 3] = "thigh"
         r[j0 + 3] = [0, 0, -knee_off]         # knee -> shin
-        g[j0 + 4] = [_capsule([0, 0, -0.02], [0, 0, -0.02 - shin], P["shin_radius"])]
+        g[j0 + 4] = [("capsule", [0, 0, -0.02], [0, 0, -0.02 - shin], P["shin_radius"])]
         grp[j0 + 4] = "shin"
         r[j0 + 4] = [0, 0, -ankle_off]        # ankle -> foot
-        g[j0 + 5] = [_box([fc[0], 0, fc[1]], list(fh))]
+        g[j0 + 5] = [("box", [fc[0], 0, fc[1]], list(fh))]
         grp[j0 + 5] = "foot"
     # ---- arms
     upper = P["upper_arm"] * scale_arm
@@ -242,12 +245,22 @@ def _humanoid_at_density(P):
         r[j0 + 1] = [0, 0, 0]
         g[j0 + 2] = []
         r[j0 + 2] = [0, 0, 0]
-        g[j0 + 3] = [_capsule([0, 0, 0], [0, 0, -upper], 0.04)]
+        g[j0 + 3] = [("capsule", [0, 0, 0], [0, 0, -upper], 0.04)]
         grp[j0 + 3] = "upper_arm"
         r[j0 + 3] = [0, 0, -upper]
-        g[j0 + 4] = [_capsule([0, 0, 0], [0, 0, -lower], 0.031), _sphere([0, 0, -lower - 0.02], 0.04)]
+        g[j0 + 4] = [("capsule", [0, 0, 0], [0, 0, -lower], 0.031), ("sphere", [0, 0, -lower - 0.02], 0.04)]
         grp[j0 + 4] = "lower_arm"
 
+    return g, grp, r
+
+
+_PRIMITIVES = {"capsule": _capsule, "sphere": _sphere, "box": _box}
+
+
+def _humanoid_at_density(P):
+    mass_scale = P["mass_scale"]
+    shapes, grp, r = _layout(P)
+    g = {b: [_PRIMITIVES[s[0]](*s[1:]) for s in shapes[b]] for b in shapes}
     mass = np.zeros(NB)
     com = np.zeros((NB, 3))
     inertia_o = np.zeros((NB, 3, 3))
@@ -337,6 +350,29 @@ def build(kind, overrides=None, use_identified=True):
     m["axis"] = np.array(AXIS, np.int32)
     m["stand_height"] = standing_height(m)
     return m
+
+
+def visual_geoms(kind, overrides=None, use_identified=True):
+    """The primitives that make up the robot, as drawn (docs/RENDER.md): a list of (body, type, params) in the link frame of `body`,
+    params a dict of float64 arrays -- capsule {p0, p1, r}, sphere {c, r}, box {c, half}.  They are the very shapes whose masses and
+    inertias build() composes (same specification, same overrides); massless bodies have none."""
+    if kind not in DEFAULTS:
+        raise ValueError("unknown robot kind %r" % (kind,))
+    ov = dict(identified(kind)) if use_identified else {}
+    ov.update(overrides or {})
+    shapes, _, _ = _layout(params(kind, ov))
+    names = {"capsule": ("p0", "p1", "r"), "sphere": ("c", "r"), "box": ("c", "half")}
+    out = []
+    for b in range(NB):
+        for s in shapes[b]:
+            out.append((b, s[0], {k: np.asarray(v, float) for k, v in zip(names[s[0]], s[1:])}))
+    return out
+
+
+def body_groups(kind="walker3d"):
+    """body -> its mass group (MASS_GROUPS), None for the massless intermediate links."""
+    _, grp, _ = _layout(params(kind))
+    return [grp.get(b) for b in range(NB)]
 
 
 def _rot(axis, q):
