@@ -44,10 +44,10 @@ def hipcc():
     return "hipcc"
 
 
-def stale():
-    if not os.path.exists(LIB):
+def stale(lib=LIB):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
+    t = os.path.getmtime(lib)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
@@ -82,19 +82,11 @@ def _compile_lib(out, extra_flags, tag, verbose):
     return out
 
 
-def _stale(lib):
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
-
-
 def build_fuzz(force=False, verbose=False):
     """The -DSS_FUZZ_SCHED build of the same sources (lib/libsteppingstone_fuzz.so): every wavefront sleeps a pseudo-random time at the
     start of each barrier window.  TEST BUILD -- tests/test_gpu_sched_fuzz.py requires its results to be bit-identical to the
     product library's; nothing in the package loads it."""
-    if not force and not _stale(FUZZ_LIB):
+    if not force and not stale(FUZZ_LIB):
         return FUZZ_LIB
     os.makedirs(LIBDIR, exist_ok=True)
     return _compile_lib(FUZZ_LIB, ["-DSS_FUZZ_SCHED"], "_fuzz", verbose)

@@ -20,6 +20,143 @@ hipError_t launch_render(const Params& P, int kind, const int32_t* env_ids, int 
 hipError_t launch_body_poses(const Params& P, int kind, float* out, hipStream_t st);
 }  // namespace ss
 
+// The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
+// exist in its code object alone.
+namespace ss {
+
+// Consumer side of the peer-store all-gather: lane r waits until peer r has published `value` (or a later step) in this
+// rank's flag array.  Bounded spin: on time-out it raises *error instead of hanging the GPU.
+static __global__ void peer_wait_kernel(const uint32_t* flags, int count, uint32_t value, uint32_t* error) {
+  const int r = threadIdx.x;
+  if (r >= count) return;
+  for (long long it = 0; it < (1ll << 23); ++it) {     // ~1 s
+    const uint32_t v = __hip_atomic_load(flags + r, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((int32_t)(v - value) >= 0) return;
+    __builtin_amdgcn_s_sleep(8);
+  }
+  *error = 1u + (uint32_t)r;
+}
+
+// hook updates, stream-ordered
+static __global__ void set_knobs_kernel(Knobs* dst, Knobs v) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
+}
+// per-env sampling grids: [N][121] row-major (the caller's layout, playground/train.py:267-271) -> [121][Npad]
+static __global__ void transpose_prob_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int npad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * SS_NCELL) return;
+  const int e = i / SS_NCELL, k = i - e * SS_NCELL;
+  dst[(size_t)k * npad + e] = src[i];
+}
+static __global__ void copy_prob_kernel(const float* __restrict__ src, float* __restrict__ dst) {
+  if (threadIdx.x < SS_NCELL) dst[threadIdx.x] = src[threadIdx.x];
+}
+
+// one thread per (env, grid cell): PHYSICS.md section 8
+// create_temp_states (common/envs_utils.py:573-578, playground/train.py:247-257): per env the 121 variants of the
+// current observation with the look-ahead stone moved to each (yaw, pitch) grid cell.  Only obs[55..59] differ:
+// obs_kernel first writes the current observation rows (lane per env, coalesced state loads) to a scratch [N,60];
+// then one 256-thread workgroup per env computes the 121 x 5 target features (one lane per cell) and streams the
+// [121,60] block out as 1815 coalesced float4 -- the one HBM-bound kernel of the path (29 KB written per env).
+constexpr int kTempThreads = 240;      // a multiple of 15: every thread keeps ONE float4 column of the row
+static __global__ __launch_bounds__(kTempThreads) void temp_states_kernel(Params P, const float* __restrict__ obs_rows, float* out) {
+  __shared__ __attribute__((aligned(16))) float base[SS_OBS_DIM];
+  __shared__ float feat[SS_NCELL * 5];
+  const int e = blockIdx.x, t = threadIdx.x;
+  const size_t np = (size_t)P.npad;
+  if (t < SS_OBS_DIM) base[t] = obs_rows[(size_t)e * SS_OBS_DIM + t];
+  if (t < SS_NCELL) {
+    const int cell = t;
+    float pos[3], quat[4], p1[3], p2[3], tilt2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pos[i] = P.fstate[e + (F_POS + i) * np];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) quat[i] = P.fstate[e + (F_QUAT + i) * np];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { p1[i] = P.fstate[e + (F_STONE + 8 + i) * np]; p2[i] = P.fstate[e + (F_STONE + 16 + i) * np]; }
+    tilt2[0] = P.fstate[e + (F_STONE + 16 + 6) * np];
+    tilt2[1] = P.fstate[e + (F_STONE + 16 + 7) * np];
+    const int n = P.istate[e + I_N * np];
+    if (n + 1 <= kNumStones - 1) {
+      const float* T = P.terrain + e;
+      const float phi_n = n < P.istate[e + I_PROV * np] ? T[(n * 6 + 3) * np] : 0.f;      // a provisional stone is not stored
+      float phi = phi_n + yaw_sample(cell / SS_GRID), pitch = pitch_sample(cell % SS_GRID);
+      float dr = P.fstate[e + F_NNDR * np];
+      float sp, cp, sph, cph;
+      sincosf(pitch, &sp, &cp);
+      sincosf(phi, &sph, &cph);
+      float planar = dr * cp;
+      p2[0] = p1[0] + planar * cph;
+      p2[1] = p1[1] + planar * sph;
+      p2[2] = p1[2] + dr * sp;
+    }
+    float cyaw, syaw;                      // yaw only: (cos, sin) = (A, B) / |(A, B)| as in quat_roll_pitch_cs
+    {
+      const float A = 1.f - 2.f * (quat[2] * quat[2] + quat[3] * quat[3]), B = 2.f * (quat[0] * quat[3] + quat[1] * quat[2]);
+      const float n2 = A * A + B * B, inv = rsqrtf(fmaxf(n2, 1e-30f));
+      cyaw = n2 > 1e-30f ? A * inv : 1.f;
+      syaw = n2 > 1e-30f ? B * inv : 0.f;
+    }
+    float f[5];
+    target_features(pos, cyaw, syaw, p2, tilt2, f);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) feat[cell * 5 + i] = f[i];
+  }
+  __syncthreads();
+  // Measured in round 2 (profiles/r02_*_temp_states.txt): this one-workgroup-per-env shape writes 5.0-5.3 TB/s at 32768
+  // envs (a torch fill of the same buffer: 6.9 TB/s) -- and it stays there with the feature computation removed, with 60-
+  // or 120-thread workgroups, with persistent workgroups (4.1-5.0 TB/s) and with one workgroup per 16 rows (1.8 TB/s,
+  // latency-bound): the limit is the write pattern of 29,040-byte blocks, not the prologue.
+  constexpr int kRow4 = SS_OBS_DIM / 4;                      // 15 float4 per row
+  static_assert(kTempThreads % kRow4 == 0, "a thread must stay in its column");
+  constexpr int kRowsPerPass = kTempThreads / kRow4;
+  float4* o4 = reinterpret_cast<float4*>(out) + (size_t)e * (SS_NCELL * kRow4);
+  const float4* b4 = reinterpret_cast<const float4*>(base);
+  const int c4 = t % kRow4;
+  const float4 bv = b4[c4 < kRow4 - 1 ? c4 : kRow4 - 2];     // this thread's column of the common part, in registers
+#pragma unroll 1
+  for (int row = t / kRow4; row < SS_NCELL; row += kRowsPerPass) {
+    float4 v = bv;
+    const float* f = feat + row * 5;
+    if (c4 == kRow4 - 2) v.w = f[0];                         // obs[52..54], obs[55]
+    if (c4 == kRow4 - 1) v = make_float4(f[1], f[2], f[3], f[4]);
+    o4[row * kRow4 + c4] = v;          // plain stores: nontemporal ones measured 20 % slower here
+  }
+}
+
+static __global__ void random_actions_kernel(Params P, uint64_t t, float* act) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= P.n) return;
+#pragma unroll
+  for (int b = 0; b < 6; ++b) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)(6u * (uint32_t)t + b), 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int j = b * 4 + i;
+      if (j < NJ) act[(size_t)e * NJ + j] = 2.f * u01(r[i]) - 1.f;
+    }
+  }
+}
+
+// PMC calibration: a dword-per-lane coalesced copy with the step kernel's access shape (tools/hbm_traffic.py)
+static __global__ void calib_copy_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = in[i] + 1.0f;
+}
+
+// packed [N,186] <-> structure of arrays (pack_env / unpack_env)
+static __global__ void pack_state_kernel(Params P, float* packed) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < P.n) pack_env(P, e, packed);
+}
+static __global__ void unpack_state_kernel(Params P, const float* packed) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < P.n) unpack_env(P, e, packed);
+}
+
+}  // namespace ss
+
 
 namespace {
 
@@ -102,56 +239,40 @@ int helpers_for(const ss_env* env, int groups) {
 
 inline dim3 grid64(const ss_env* env) { return dim3(env->P.npad / ss::kWave); }
 
-template <bool RANDOM>
-int launch_step(ss_env* env, const ss::StepIO& io, hipStream_t st) {
+// A step or rollout launch: kernel_of(helpers) is the robot's kernel with that many helper wavefronts, launched with 1 + helpers
+// wavefronts per workgroup.  helpers_for() gives 0, 1 or 3; a forced SS_HELPERS of 2 or more than 3 runs the one-helper kernel.
+using StepKernel = void (*)(ss::Params, ss::StepIO);
+template <class KernelOf>
+int launch_env_kernel(ss_env* env, const ss::StepIO& io, hipStream_t st, KernelOf&& kernel_of) {
   // two lanes per env: 32 envs per 64-lane wavefront.  ceil(n / 32) workgroups, NOT npad / 32: the arrays are padded to 64 envs, and
   // for n mod 64 in 1..32 the padding used to launch one workgroup without a single valid env (see emit_outputs: nvalid).
   const dim3 grid((env->P.n + ss::kEnvsPerWave - 1) / ss::kEnvsPerWave);
   SS_HIP(hipSetDevice(env->device));                   // the stream belongs to this device
-  const int helpers = helpers_for(env, (int)grid.x);
-  if (helpers == 3) {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 3>), grid, dim3(4 * ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::step_kernel_helped<ss::ModelMike, RANDOM, 3>), grid, dim3(4 * ss::kWave), 0, st, env->P, io);
-  } else if (helpers > 0) {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 1>), grid, dim3(2 * ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::step_kernel_helped<ss::ModelMike, RANDOM, 1>), grid, dim3(2 * ss::kWave), 0, st, env->P, io);
-  } else {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::step_kernel<ss::ModelWalker3D, RANDOM>), grid, dim3(ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::step_kernel<ss::ModelMike, RANDOM>), grid, dim3(ss::kWave), 0, st, env->P, io);
-  }
+  const int h = helpers_for(env, (int)grid.x);
+  const int helpers = h == 3 ? 3 : (h > 0 ? 1 : 0);
+  hipLaunchKernelGGL(kernel_of(helpers), grid, dim3(ss::kWave * (1 + helpers)), 0, st, env->P, io);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
 
+template <bool RANDOM>
+int launch_step(ss_env* env, const ss::StepIO& io, hipStream_t st) {
+  const bool w = env->kind == SS_WALKER3D;
+  return launch_env_kernel(env, io, st, [w](int helpers) -> StepKernel {
+    if (helpers == 3) return w ? ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 3> : ss::step_kernel_helped<ss::ModelMike, RANDOM, 3>;
+    if (helpers == 1) return w ? ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 1> : ss::step_kernel_helped<ss::ModelMike, RANDOM, 1>;
+    return w ? ss::step_kernel<ss::ModelWalker3D, RANDOM> : ss::step_kernel<ss::ModelMike, RANDOM>;
+  });
+}
+
 // io.nsteps control steps in one launch, actions from the benchmark Philox stream
 int launch_rollout(ss_env* env, const ss::StepIO& io, hipStream_t st) {
-  const dim3 grid((env->P.n + ss::kEnvsPerWave - 1) / ss::kEnvsPerWave);
-  SS_HIP(hipSetDevice(env->device));
-  const int helpers = helpers_for(env, (int)grid.x);
-  if (helpers == 3) {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::rollout_kernel_helped<ss::ModelWalker3D, 3>), grid, dim3(4 * ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::rollout_kernel_helped<ss::ModelMike, 3>), grid, dim3(4 * ss::kWave), 0, st, env->P, io);
-  } else if (helpers > 0) {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::rollout_kernel_helped<ss::ModelWalker3D, 1>), grid, dim3(2 * ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::rollout_kernel_helped<ss::ModelMike, 1>), grid, dim3(2 * ss::kWave), 0, st, env->P, io);
-  } else {
-    if (env->kind == SS_WALKER3D)
-      hipLaunchKernelGGL((ss::rollout_kernel<ss::ModelWalker3D>), grid, dim3(ss::kWave), 0, st, env->P, io);
-    else
-      hipLaunchKernelGGL((ss::rollout_kernel<ss::ModelMike>), grid, dim3(ss::kWave), 0, st, env->P, io);
-  }
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  const bool w = env->kind == SS_WALKER3D;
+  return launch_env_kernel(env, io, st, [w](int helpers) -> StepKernel {
+    if (helpers == 3) return w ? ss::rollout_kernel_helped<ss::ModelWalker3D, 3> : ss::rollout_kernel_helped<ss::ModelMike, 3>;
+    if (helpers == 1) return w ? ss::rollout_kernel_helped<ss::ModelWalker3D, 1> : ss::rollout_kernel_helped<ss::ModelMike, 1>;
+    return w ? ss::rollout_kernel<ss::ModelWalker3D> : ss::rollout_kernel<ss::ModelMike>;
+  });
 }
 
 }  // namespace

@@ -34,14 +34,7 @@ constexpr float kGrav = 9.8f;
 constexpr float kPlankA = kStonePlankHalfLength, kPlankB = kStonePlankHalfWidth;
 // PHYSICS.md 3.4: 5 sweeps, warm-started from the previous substep of the same control step (Bullet's
 // numSolverIterations = 5 with warm starting; rounds 1-4 ran 8 cold sweeps -- DESIGN.md section 5.1 has the measured trade)
-#ifndef SS_PGS_ITERS
-#define SS_PGS_ITERS 5
-#endif
-#ifndef SS_PGS_WARM
-#define SS_PGS_WARM 1
-#endif
-constexpr int kPgsIters = SS_PGS_ITERS;
-constexpr bool kPgsWarm = SS_PGS_WARM != 0;
+constexpr int kPgsIters = 5;
 constexpr float kErp = 0.2f;
 constexpr float kSlop = 0.001f;
 constexpr float kVcorrMax = 2.0f;
@@ -93,14 +86,7 @@ static_assert(S_END <= (kLdsSlots - kSlotsA) * 4, "LDS scalar region overflow");
 // Where the warm-start impulses live between the substeps of a control step: in registers where there is room (three helper
 // wavefronts: 192 - 205 of 256 AGPRs), in the lane's LDS scalars otherwise (the plain and the one-helper rollout kernels sit at
 // 252 - 255 AGPRs and would spill 20 - 40 B per lane; 13 ds_write + 13 ds_read per substep instead).  Values are the same either way.
-#ifndef SS_CS_PER_HELPER
-#define SS_CS_PER_HELPER 6      // three-helper variants: 6 = helpers 1 and 2 evaluate six cos / sin pairs each, helper 0 idles; 4 = all three
-                                // take four each (ss_rollout3.hip sets it for the rollout kernel: measured per kernel, see there)
-#endif
-#ifndef SS_WARM_LDS_BELOW
-#define SS_WARM_LDS_BELOW 3
-#endif
-constexpr bool warm_in_lds(int helpers) { return helpers < SS_WARM_LDS_BELOW; }
+constexpr bool warm_in_lds(int helpers) { return helpers < 3; }
 
 // the half-tree: global (right-side) joint ids, spine first
 constexpr int kHalf[NH] = {0, 1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 16};
@@ -178,13 +164,10 @@ __device__ __forceinline__ void ss_fuzz(uint32_t site) {
 #define SS_FUZZ(site) ((void)0)
 #endif
 
-// cos / sin of the joint angles on the helper wavefronts (and the joint torques ahead of them on the main one) from this many
-// helpers on.  Measured: with three helpers 0.0598 -> 0.0581 ms/step at 4096 envs; a single helper that also evaluates the 12
-// cos / sin is slower than leaving them on the main wavefront (16384 envs, rollout kernel: 0.0631 vs 0.0608 ms/step).
-#ifndef SS_CS_OFFLOAD_MIN
-#define SS_CS_OFFLOAD_MIN 3
-#endif
-constexpr bool cs_offload(int helpers) { return helpers >= SS_CS_OFFLOAD_MIN; }
+// cos / sin of the joint angles on the helper wavefronts (and the joint torques ahead of them on the main one) with three helpers.
+// Measured: with three helpers 0.0598 -> 0.0581 ms/step at 4096 envs; a single helper that also evaluates the 12 cos / sin is
+// slower than leaving them on the main wavefront (16384 envs, rollout kernel: 0.0631 vs 0.0608 ms/step).
+constexpr bool cs_offload(int helpers) { return helpers >= 3; }
 
 struct Lds {       // lane-private view of the workgroup's LDS
   float* base;
@@ -333,9 +316,9 @@ SSD JRec opaque_rec(const JRec& r) {
   o.Uw[0] = w0; o.Uw[1] = w1; o.Uw[2] = w2; o.Uv[0] = v0; o.Uv[1] = v1; o.Uv[2] = v2;
   return o;
 }
-#ifndef SS_PIN
-#define SS_PIN(J) ((J) == 7)
-#endif
+// the ankle's (joint 7) record passes through opaque registers at its uses: otherwise it stays in scratch, 32 B per lane per substep
+// (docs/HISTORY.md, round 3; for every record it costs 120 v_mov per column pair)
+constexpr bool pin_joint(int J) { return J == 7; }
 // two columns at once in packed f32: the unloaded down step applies the same joint operator to every column of T, so
 // a pair of columns shares each instruction (v_pk_*), coefficients broadcast
 template <class Model, int J>
@@ -344,7 +327,7 @@ SSD SV2 imp_down_pair(const JointCache& jc, const SV2& p) {
   constexpr float rx = Model::r[J][0], ry = Model::r[J][1], rz = Model::r[J][2];
   const JRec& r = jc.r[k];
   float c = r.cs, s = r.sn;
-  if constexpr (SS_PIN(J)) { SS_REG(c); SS_REG(s); }
+  if constexpr (pin_joint(J)) { SS_REG(c); SS_REG(s); }
   SV2 d;
   d.w[ax] = p.w[ax];
   d.w[ai] = p.w[ai] * c + p.w[aj] * s;
@@ -365,7 +348,7 @@ SSD SV2 imp_down_pair(const JointCache& jc, const SV2& p) {
   // overlapping <2 x float> load, and the record then stays in scratch (the ankle record did: 32 B per helper lane stored and
   // re-loaded every substep and written back at the end of every launch)
   float uw0 = r.Uw[0], uw1 = r.Uw[1], uw2 = r.Uw[2], uv0 = r.Uv[0], uv1 = r.Uv[1], uv2 = r.Uv[2], di = r.Dinv;
-  if constexpr (SS_PIN(J)) { SS_REG(uw0); SS_REG(uw1); SS_REG(uw2); SS_REG(uv0); SS_REG(uv1); SS_REG(uv2); SS_REG(di); }
+  if constexpr (pin_joint(J)) { SS_REG(uw0); SS_REG(uw1); SS_REG(uw2); SS_REG(uv0); SS_REG(uv1); SS_REG(uv2); SS_REG(di); }
   ssf2 dotv = d.w[0] * uw0 + d.w[1] * uw1 + d.w[2] * uw2 + d.v[0] * uv0 + d.v[1] * uv1 + d.v[2] * uv2;
   d.w[ax] -= dotv * di;
   return d;
@@ -378,7 +361,7 @@ SSD SV2 imp_up_pair(const JointCache& jc, ssf2* ul2, const SV2& p) {
   const JRec& r = jc.r[k];
   float c = r.cs, s = r.sn, di = r.Dinv;
   float uw[3] = {r.Uw[0], r.Uw[1], r.Uw[2]}, uv[3] = {r.Uv[0], r.Uv[1], r.Uv[2]};
-  if constexpr (SS_PIN(J)) {
+  if constexpr (pin_joint(J)) {
     SS_REG(c); SS_REG(s); SS_REG(di);
 #pragma unroll
     for (int i = 0; i < 3; ++i) { SS_REG(uw[i]); SS_REG(uv[i]); }
@@ -408,7 +391,7 @@ SSD SV2 imp_down_pair_loaded(const JointCache& jc, const ssf2* ul2, const SV2& p
   const JRec& r = jc.r[k];
   SV2 d = imp_down_pair<Model, J>(jc, p);            // includes  - Dinv * (U . d)
   float di = r.Dinv;
-  if constexpr (SS_PIN(J)) SS_REG(di);
+  if constexpr (pin_joint(J)) SS_REG(di);
   d.w[ax] += ul2[k] * di;
   return d;
 }
@@ -687,7 +670,7 @@ SSD void jacobian_rows(const DetectOut& det, const Lds& L, ssf2 (&rWp)[12][3], f
 
 #ifndef SS_HOST_HARNESS
 // Helper wavefronts of the small-batch variant (one workgroup = main wavefront + HELPERS helpers, five barriers per substep):
-//   #0 state of the substep is in LDS         helpers 1, 2: cos / sin of the joint angles -> LDS (main: joint torques)
+//   #0 state of the substep is in LDS         helpers: cos / sin of the joint angles -> LDS (main: joint torques)
 //   #0b                                        helper 0: forward kinematics, contact detection -> LDS
 //   #1 leg joint records are handed over      helper h: operators of column pair h, part A (T, impulses up to the pelvis)
 //   #2 spine records + base factor as well    part B (G, Lambda_own)
@@ -695,24 +678,26 @@ SSD void jacobian_rows(const DetectOut& det, const Lds& L, ssf2 (&rWp)[12][3], f
 // while the main wavefront runs cos / sin, pass 1 and the leg half of pass 2 | the spine and the base solve | pass 3, the foot
 // twist and the Jacobian rows | the PGS and the rest.
 // `extra(helper)` runs between #0b and #1, where helpers 1 and 2 are idle: the rollout kernel draws the next step's actions there
-// (last helper) and emits the previous step's outputs (helper 1, three-helper variant).
-template <class Model, int HELPERS, class Extra>
+// (helper 1) and emits the previous step's outputs (the last helper, three-helper variant).
+// CS_PER: how many of the 12 cos / sin pairs each evaluating helper takes (three helpers).  6: helpers 1 and 2, helper 0 idles; 4: all
+// three.  A property of the kernel, measured per kernel (step_kernel_helped: 6, rollout_kernel_helped: 4; see ss_rollout3.hip).
+template <class Model, int HELPERS, int CS_PER, class Extra>
 __device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&& extra) {
+  static_assert(CS_PER == 4 || CS_PER == 6, "the 12 cos / sin pairs go to three helpers (4 each) or to two (6 each)");
   __syncthreads();                                   // #0
   SS_FUZZ(0x10u + helper);
-  if constexpr (cs_offload(HELPERS)) {   // cos / sin of the 12 joint angles for everybody: helpers 1 and 2 six each, or (SS_CS_PER_HELPER
-                                         // = 4, the rollout kernel's unit) all three helpers four each
-    constexpr int kPer = HELPERS >= 3 ? SS_CS_PER_HELPER : NH;
-    const int first = HELPERS >= 3 ? (SS_CS_PER_HELPER == 4 ? helper * 4 : (helper - 1) * 6) : 0;
-    if (HELPERS < 3 || SS_CS_PER_HELPER == 4 || helper >= 1) {
-      float qh[kPer], c_[kPer], s_[kPer];
+  if constexpr (cs_offload(HELPERS)) {   // cos / sin of the 12 joint angles for everybody
+    constexpr int kIdle = HELPERS - NH / CS_PER;     // helpers 0 .. kIdle - 1 evaluate none
+    const int first = (helper - kIdle) * CS_PER;
+    if (kIdle == 0 || helper >= kIdle) {
+      float qh[CS_PER], c_[CS_PER], s_[CS_PER];
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) qh[k] = L.s(S_Q + first + k);
+      for (int k = 0; k < CS_PER; ++k) qh[k] = L.s(S_Q + first + k);
       SS_MEMBAR();
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) ss_sincos(qh[k], s_[k], c_[k]);
+      for (int k = 0; k < CS_PER; ++k) ss_sincos(qh[k], s_[k], c_[k]);
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) { L.hs(kHandCs + first + k) = c_[k]; L.hs(kHandCs + NH + first + k) = s_[k]; }
+      for (int k = 0; k < CS_PER; ++k) { L.hs(kHandCs + first + k) = c_[k]; L.hs(kHandCs + NH + first + k) = s_[k]; }
     }
     __syncthreads();                                 // #0b
     SS_FUZZ(0x20u + helper);
@@ -1259,11 +1244,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
   for (int i = 0; i < 3; ++i) { dv0.w[i] = 0.f; dv0.v[i] = 0.f; }
   const int active = det.active;
   const int pair_active = active | xchg_i(active);   // both lanes must take the contact branch together
-#ifdef SS_ABLATE_CONTACT
-  const bool in_contact = false;
-#else
   const bool in_contact = pair_active != 0;
-#endif
   ssf2 Lc[6][3];                       // column b of Lambda_own as three pairs
   SS_PROF(7);
   // What does not need the contact operators: with helper wavefronts it overlaps part B of their work.
@@ -1303,20 +1284,18 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       float wlam_prev[4][3];           // the previous substep's impulses
       int wkey_prev = 0;
       auto load_warm = [&]() {
-        if constexpr (kPgsWarm) {
-          if constexpr (warm_in_lds(HELPERS)) {
-            wkey_prev = __builtin_bit_cast(int, L.s(S_WKEY));
+        if constexpr (warm_in_lds(HELPERS)) {
+          wkey_prev = __builtin_bit_cast(int, L.s(S_WKEY));
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+          for (int k = 0; k < 4; ++k)
 #pragma unroll
-              for (int d = 0; d < 3; ++d) wlam_prev[k][d] = L.s(S_WLAM + 3 * k + d);
-          } else {
-            wkey_prev = wm.key;
+            for (int d = 0; d < 3; ++d) wlam_prev[k][d] = L.s(S_WLAM + 3 * k + d);
+        } else {
+          wkey_prev = wm.key;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+          for (int k = 0; k < 4; ++k)
 #pragma unroll
-              for (int d = 0; d < 3; ++d) wlam_prev[k][d] = wm.lam[k][d];
-          }
+            for (int d = 0; d < 3; ++d) wlam_prev[k][d] = wm.lam[k][d];
         }
       };
       // with helper wavefronts the loads are issued here and their LDS latency hides behind the rows; the plain variant has no
@@ -1361,7 +1340,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       int warm_any = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const bool w = kPgsWarm && (((active & wkey_prev) >> k) & 1);
+        const bool w = ((active & wkey_prev) >> k) & 1;
         warm_any |= w ? 1 : 0;
 #pragma unroll
         for (int d = 0; d < 3; ++d) lam[k][d] = w ? wlam_prev[k][d] : 0.f;
@@ -1395,11 +1374,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
 #pragma unroll
         for (int i = 0; i < 3; ++i) Wp[i] += dWp[i];
       };
-#ifdef SS_PGS_NO_PEEL
-      constexpr int kCoupled = kPgsIters;
-#else
       constexpr int kCoupled = kPgsIters - 1;   // after the last sweep nothing reads the foot twist any more: its coupling is dead
-#endif
       ssf2 Cc[6][3];                   // read once (the compiler parks what does not fit in AGPRs: 0.0514 -> 0.0511 ms/step)
 #pragma unroll
       for (int l = 0; l < 6; ++l)
@@ -1409,26 +1384,24 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       // all LDS reads land before the loop: otherwise its body carries eleven `s_waitcnt lgkmcnt(n)` for the first iteration's sake
       __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0), leave vmcnt / expcnt alone
 #endif
-      if constexpr (kPgsWarm) {
-        // the starting impulses move both feet before the first sweep: the own foot through y = Lambda_own w, the partner's foot
-        // through C (like a sweep's increments).  A lane pair without a warm corner skips it (the products would add zeros).
-        if ((warm_any | xchg_i(warm_any)) != 0) {
-          static_for<0, 12>([&](auto Rc) {
-            constexpr int row = decltype(Rc)::value, k = row / 3, d = row % 3;
-            const ssf2 l2 = {lam[k][d], lam[k][d]};
+      // the starting impulses move both feet before the first sweep: the own foot through y = Lambda_own w, the partner's foot
+      // through C (like a sweep's increments).  A lane pair without a warm corner skips it (the products would add zeros).
+      if ((warm_any | xchg_i(warm_any)) != 0) {
+        static_for<0, 12>([&](auto Rc) {
+          constexpr int row = decltype(Rc)::value, k = row / 3, d = row % 3;
+          const ssf2 l2 = {lam[k][d], lam[k][d]};
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { Vp[i] = rYp[row][i] * l2 + Vp[i]; Wp[i] = rWp[row][i] * l2 + Wp[i]; }
-          });
-          ssf2 Wo[3];
+          for (int i = 0; i < 3; ++i) { Vp[i] = rYp[row][i] * l2 + Vp[i]; Wp[i] = rWp[row][i] * l2 + Wp[i]; }
+        });
+        ssf2 Wo[3];
 #pragma unroll
-          for (int i = 0; i < 3; ++i) Wo[i] = ssf2{xchg(Wp[i].x), xchg(Wp[i].y)};
+        for (int i = 0; i < 3; ++i) Wo[i] = ssf2{xchg(Wp[i].x), xchg(Wp[i].y)};
 #pragma unroll
-          for (int l = 0; l < 6; ++l) {
-            const float sc = (l & 1) ? Wo[l >> 1].y : Wo[l >> 1].x;
-            const ssf2 s2 = {sc, sc};
+        for (int l = 0; l < 6; ++l) {
+          const float sc = (l & 1) ? Wo[l >> 1].y : Wo[l >> 1].x;
+          const ssf2 s2 = {sc, sc};
 #pragma unroll
-            for (int i = 0; i < 3; ++i) Vp[i] = Cc[l][i] * s2 + Vp[i];
-          }
+          for (int i = 0; i < 3; ++i) Vp[i] = Cc[l][i] * s2 + Vp[i];
         }
       }
 #pragma unroll 1                       // (unrolled by 2 or fully: 0.0522 vs 0.0504 ms/step; C formed by the helpers after barrier #3
@@ -1449,28 +1422,24 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
           }
         }
       }
-#ifndef SS_PGS_NO_PEEL
       sweep();
-#endif
       SV W = {{Wp[0].x, Wp[0].y, Wp[1].x}, {Wp[1].y, Wp[2].x, Wp[2].y}};
-      if constexpr (kPgsWarm) {        // what the next substep of this control step starts from
-        if constexpr (warm_in_lds(HELPERS)) {
+      // what the next substep of this control step starts from
+      if constexpr (warm_in_lds(HELPERS)) {
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int d = 0; d < 3; ++d) L.s(S_WLAM + 3 * k + d) = lam[k][d];
-          L.s(S_WKEY) = __builtin_bit_cast(float, key);
-        } else {
+          for (int d = 0; d < 3; ++d) L.s(S_WLAM + 3 * k + d) = lam[k][d];
+        L.s(S_WKEY) = __builtin_bit_cast(float, key);
+      } else {
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int d = 0; d < 3; ++d) wm.lam[k][d] = lam[k][d];
-          wm.key = key;
-        }
+          for (int d = 0; d < 3; ++d) wm.lam[k][d] = lam[k][d];
+        wm.key = key;
       }
       SS_PROF(9);
       // accumulated foot wrenches -> whole tree: own leg up, pelvis biases summed over the pair, spine, base, down
-#ifndef SS_ABLATE_FINAL
       {
         SV p = {{-W.w[0], -W.w[1], -W.w[2]}, {-W.v[0], -W.v[1], -W.v[2]}};
         static_rfor<7, 3>([&](auto Jc) { p = imp_up<Model, decltype(Jc)::value>(jc, ul, p); });
@@ -1490,9 +1459,8 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
           d = imp_down<Model, j, false>(jc, ul, d, &dqd[half_pos(j)]);
         });
       }
-#endif
   };
-  if (kPgsWarm && !in_contact) {                 // no contact in this substep: nothing to start the next one from
+  if (!in_contact) {                 // no contact in this substep: nothing to start the next one from
     if constexpr (warm_in_lds(HELPERS)) L.s(S_WKEY) = 0.f;
     else wm.key = 0;
   }

@@ -14,18 +14,6 @@
 //   prob   [121] float shared grid, or [121][Npad] per-env grids
 #pragma once
 #include "ss_dynamics.hpp"
-// Two tuning options measured in round 6 and NOT adopted (profiles/r06_ab_disc_vs_plank_variants.txt): the benchmark actions' six Philox
-// blocks split between the lanes of a pair (-0.4 % / -0.6 % at 4096 envs, +0.9 % in the plain K-step kernel), and the one-launch-per-
-// step kernel's output stage on a helper wavefront (SS_STEP_EMIT_OFFLOAD below: no gain, as in round 3).
-#ifndef SS_SPLIT_ACTION_PHILOX
-#define SS_SPLIT_ACTION_PHILOX 0
-#endif
-#ifndef SS_EMIT_ON_LAST_HELPER
-#define SS_EMIT_ON_LAST_HELPER 1
-#endif
-#ifndef SS_NUM_SUBSTEPS
-#define SS_NUM_SUBSTEPS 4
-#endif
 #include "../../include/steppingstone.h"
 
 namespace ss {
@@ -34,6 +22,7 @@ enum { F_POS = 0, F_QUAT = 3, F_VEL = 7, F_Q = 13, F_QD = 34, F_POT = 55, F_ZINI
        F_STONE = 59, F_HEAD = 59 + 24, F_EPRET_LO = 59 + 30, NF = 59 + 30 + 1 };
 enum { I_N = 0, I_COUNT = 1, I_ELAPSED = 2, I_RNG = 3, I_FLAGS = 4, I_PROV = 5, NI = 6 };
 constexpr int kNumStones = 20;
+constexpr int kNumSubsteps = 4;        // per control step (PHYSICS.md 1: 1/60 s = 4 x 1/240 s)
 constexpr float kDeg = 0.017453292519943295f;
 
 // What the hooks (update_curriculum / update_specialist / update_sample_prob / set_robot_params / auto-reset switch)
@@ -358,30 +347,6 @@ SSD float reset_angle(const uint32_t (&r)[6][4]) {
   return fminf(fmaxf(q, lo), hi);
 }
 
-// Global stores of a step's outputs and state rows.  -DSS_NT_STORES makes them non-temporal (`nt`) in the one-launch-per-step
-// kernels: nothing reads the rows again before the kernel ends, and a kernel boundary on this chip writes back whatever is dirty in
-// eight private L2s -- measured 0.0648 -> 0.0640 ms/step at 4096 envs (system-scope write-through stores: the same).  Off by
-// default: 1.2 % of a secondary figure.  (Round 3 left them off because a non-reproducible one-step mismatch had shown up next to
-// them; round 4 root-caused that to copy_block's padding workgroup, DESIGN.md 5.1b -- unrelated to the stores.)  The committed
-// profiles are of the plain stores.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(SS_NT_STORES)
-typedef float ss_v4f __attribute__((ext_vector_type(4)));
-template <bool NT, class T>
-SSD void gst(T* p, T v) {
-  if constexpr (NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
-template <bool NT>
-SSD void gst4(float4* p, float4 v) {
-  if constexpr (NT) __builtin_nontemporal_store(ss_v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<ss_v4f*>(p));
-  else *p = v;
-}
-#else
-template <bool NT, class T>
-SSD void gst(T* p, T v) { *p = v; }
-template <bool NT>
-SSD void gst4(float4* p, float4 v) { *p = v; }
-#endif
 // ---- output stage of a control step: observation / reward / done / info rows and the bulk of the state write-back ----
 struct StepOut {        // what it needs, true world, after the optional reset
   float pos[3], quat[4];
@@ -396,6 +361,14 @@ struct StepOut {        // what it needs, true world, after the optional reset
 // contiguous 256-byte stores: a lane writing its own [60]-float row directly would touch 32 partial cache lines
 // per store instruction (measured 3.1x the algorithmic HBM traffic before this).  One body for the device and for the
 // host pre-flight (tests/host/host_harness.cpp runs the 64 lanes of a wavefront as threads around the same LDS block).
+// The global stores are plain: non-temporal ones in the one-launch-per-step kernels measured 1.2 % (0.0648 -> 0.0640 ms/step at 4096
+// envs) on that secondary figure only, not adopted (docs/HISTORY.md).
+//
+// copy_out: one word (or float4) of the staged block to global memory.  By-value arguments on purpose: the address is formed before
+// the LDS load and a float4 moves as four floats -- the schedule of the copy loops that the kernels were measured with (`dst[g] =
+// lds[g]` evaluates the load first and the loops schedule differently).
+template <class T>
+SSD void copy_out(T* dst, T v) { *dst = v; }
 template <class Model, bool ROLLOUT>
 SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e, int side, bool valid, int lane, int lane_global,
                       int kstep, float* lds) {
@@ -427,8 +400,8 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
         constexpr float span = Model::hi[jr] - Model::lo[jr];
         const float ps = policy_true_sign(jr, side);
         const float mid = (side && mirror_flips(jr)) ? -midr : midr;
-        gst<!ROLLOUT>(&Fo[(F_Q + gj) * np], o.qt[k]);
-        gst<!ROLLOUT>(&Fo[(F_QD + gj) * np], o.qdt[k]);
+        Fo[(F_Q + gj) * np] = o.qt[k];
+        Fo[(F_QD + gj) * np] = o.qdt[k];
         SS_OBS(6 + gj) = clip5(2.f * (ps * o.qt[k] - ps * mid) / span);
         SS_OBS(27 + gj) = clip5(0.1f * (ps * o.qdt[k]));
       }
@@ -467,11 +440,11 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
       istage[2] = (uint32_t)o.inf.bad_transition; istage[3] = (uint32_t)o.inf.steps_reached; istage[4] = (uint32_t)o.inf.update_terrain;
       istage[5] = SS_F2U(o.inf.ep_ret_lo);
 #pragma unroll
-      for (int i = 0; i < 3; ++i) gst<!ROLLOUT>(&Fo[(F_POS + i) * np], o.pos[i]);
+      for (int i = 0; i < 3; ++i) Fo[(F_POS + i) * np] = o.pos[i];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) gst<!ROLLOUT>(&Fo[(F_QUAT + i) * np], o.quat[i]);
+      for (int i = 0; i < 4; ++i) Fo[(F_QUAT + i) * np] = o.quat[i];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) { gst<!ROLLOUT>(&Fo[(F_VEL + i) * np], o.v0.w[i]); gst<!ROLLOUT>(&Fo[(F_VEL + 3 + i) * np], o.v0.v[i]); }
+      for (int i = 0; i < 3; ++i) { Fo[(F_VEL + i) * np] = o.v0.w[i]; Fo[(F_VEL + 3 + i) * np] = o.v0.v[i]; }
     }
   }
   {
@@ -489,11 +462,11 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
         float4* d4 = reinterpret_cast<float4*>(dst);
         const float4* s4 = reinterpret_cast<const float4*>(lds);
 #pragma unroll 1
-        for (int g = lane; g < n4; g += kWave) gst4<!ROLLOUT>(&d4[g], s4[g]);
-        for (int g = (n4 << 2) + lane; g < nfl; g += kWave) gst<!ROLLOUT>(&dst[g], lds[g]);
+        for (int g = lane; g < n4; g += kWave) copy_out(&d4[g], s4[g]);
+        for (int g = (n4 << 2) + lane; g < nfl; g += kWave) copy_out(&dst[g], lds[g]);
       } else {
 #pragma unroll 1
-        for (int g = lane; g < nfl; g += kWave) gst<!ROLLOUT>(&dst[g], lds[g]);
+        for (int g = lane; g < nfl; g += kWave) copy_out(&dst[g], lds[g]);
       }
     };
     if (io.obs) {
@@ -504,7 +477,7 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
 #pragma unroll 1
         for (int g = lane; g < nvalid * SS_OBS_DIM; g += kWave) {
           const int el = g / SS_OBS_DIM, idx = g - el * SS_OBS_DIM;
-          gst<!ROLLOUT>(&og[g], lds[el * kPackW + idx]);
+          copy_out(&og[g], lds[el * kPackW + idx]);
         }
       }
     }
@@ -516,7 +489,7 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
     if (io.info) {
       uint32_t* ig = reinterpret_cast<uint32_t*>(io.info + env0);
       const uint32_t* is = reinterpret_cast<const uint32_t*>(lds) + kInfoBase;
-      for (int g = lane; g < nvalid * SS_INFO_WORDS; g += kWave) gst<!ROLLOUT>(&ig[g], is[g]);
+      for (int g = lane; g < nvalid * SS_INFO_WORDS; g += kWave) copy_out(&ig[g], is[g]);
     }
 #if defined(__HIP_DEVICE_COMPILE__)                   // the peer-store exchange exists on the device only (xGMI stores, system-scope atomics)
     if constexpr (!ROLLOUT) {
@@ -543,14 +516,13 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
 #undef SS_OBS
 }
 
-// The three-helper rollout kernel hands the output stage to helper 1: the main wavefront leaves 14 words in the hand-off region (the
-// place of the detection's Rf / pen, which that variant does not use, and the two spare words), everything else is the state in
-// LDS region B (refreshed after a reset).  Helper 1 works while the main wavefront is already in the next
+// The three-helper rollout kernel hands the output stage to a helper wavefront: the main wavefront leaves 14 words in the hand-off
+// region (the place of the detection's Rf / pen, which that variant does not use, and the two spare words), everything else is the
+// state in LDS region B (refreshed after a reset).  The helper works while the main wavefront is already in the next
 // control step (between barriers #0b and #1 of its first substep; the state in LDS changes at that substep's end only).
-#ifndef SS_STEP_EMIT_OFFLOAD
-#define SS_STEP_EMIT_OFFLOAD 0
-#endif
-constexpr bool out_offload(int helpers, bool rollout) { return (rollout || SS_STEP_EMIT_OFFLOAD) && helpers >= 3; }   // (one launch per step: 0.0697 vs 0.0687 ms inline, round 3)
+// The one-launch-per-step kernel keeps its output stage inline: on a helper it measured 0.0697 against 0.0687 ms/step (round 3), and
+// no gain again in round 6.
+constexpr bool out_offload(int helpers, bool rollout) { return rollout && helpers >= 3; }
 constexpr int kHandOut = kHandDet, kHandOut2 = kHandFloats;     // 13 + 2 words
 static_assert(kHandOut2 + 2 <= kHandSlots * 4, "hand-off region");
 #if !defined(SS_HOST_HARNESS)
@@ -594,28 +566,13 @@ __device__ __forceinline__ void emit_from_handoff(const Params& P, const StepIO&
 #endif
 
 // Benchmark actions of control step tt for this lane's half of env e (PHYSICS.md 5: six Philox blocks per env and step, 21 of the
-// 24 words -> U(-1,1)), in the lane's own (mirrored) world.
-template <bool SPLIT = false, class Write>
+// 24 words -> U(-1,1)), in the lane's own (mirrored) world.  Both lanes of the pair draw all six blocks: three per lane, exchanged (as
+// for the reset noise), measured -0.4 % / -0.6 % at 4096 envs and +0.9 % in the plain K-step kernel (round 6), not adopted.
+template <class Write>
 SSD void random_actions_half(const Params& P, int e, int side, float m, uint32_t tt, Write&& write) {
   uint32_t ra[6][4];
-  if constexpr (SPLIT && SS_SPLIT_ACTION_PHILOX) {   // three of the six blocks per lane of the pair, exchanged (integer-exact; like the reset noise): 300 instructions less per step
-      // wherever the main wavefront draws the actions itself
-    uint32_t mine[3][4];
 #pragma unroll
-    for (int b = 0; b < 3; ++b)
-      philox4x32_10(6u * tt + (side ? 3u : 0u) + b, 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, mine[b]);
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t other = xchg_u32(mine[b][i]);
-        ra[b][i] = side ? other : mine[b][i];
-        ra[3 + b][i] = side ? mine[b][i] : other;
-      }
-  } else {
-#pragma unroll
-    for (int b = 0; b < 6; ++b) philox4x32_10(6u * tt + b, 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, ra[b]);
-  }
+  for (int b = 0; b < 6; ++b) philox4x32_10(6u * tt + b, 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, ra[b]);
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
     constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);
@@ -634,7 +591,7 @@ SSD void random_actions_half(const Params& P, int e, int side, float m, uint32_t
 template <class Model, bool RANDOM_ACT, int HELPERS = 0, bool ROLLOUT = false>
 SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, float* lds) {
   static_assert(!ROLLOUT || RANDOM_ACT, "a multi-step launch draws its actions on the device");
-  constexpr bool kOffload =            // output stage on helper 1
+  constexpr bool kOffload =            // output stage on a helper wavefront
 #if defined(__HIP_DEVICE_COMPILE__)
       out_offload(HELPERS, ROLLOUT);
 #else
@@ -718,7 +675,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
         drawn = true;
       }
     }
-    if (!drawn) random_actions_half<!(HELPERS == 0 && ROLLOUT)>(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep, [&](int k, float a) { L.s(S_ACT + k) = a; });
+    if (!drawn) random_actions_half(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep, [&](int k, float a) { L.s(S_ACT + k) = a; });
   } else {
     static_for<0, NH>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value, jr = kHalf[k];
@@ -741,9 +698,9 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
 #endif
   Warm wm;                                     // contact impulses carried from substep to substep; every control step starts cold
   warm_clear(wm);
-  if constexpr (kPgsWarm && warm_in_lds(HELPERS)) L.s(S_WKEY) = 0.f;
+  if constexpr (warm_in_lds(HELPERS)) L.s(S_WKEY) = 0.f;
 #pragma unroll 1
-  for (int k = 0; k < SS_NUM_SUBSTEPS; ++k) substep<Model, HELPERS>(SS_PROF_ARG power, fr, L, wm);
+  for (int k = 0; k < kNumSubsteps; ++k) substep<Model, HELPERS>(SS_PROF_ARG power, fr, L, wm);
   SS_FUZZ(0x61u);
   SS_PROF(12);
   SS_MEMBAR();
@@ -930,11 +887,11 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
       qdt[k] = sg * L.s(S_QD + k);
     }
   });
-  // 11. output stage (emit_outputs): inline, or on helper 1 in the three-helper rollout kernel
+  // 11. output stage (emit_outputs): inline, or on a helper wavefront in the three-helper rollout kernel
   SS_PROFE(8);       // joint values of the next state
   SS_FUZZ(0x62u);
-  if constexpr (ROLLOUT || kOffload) {
-    // the LDS copy of the state is what comes next (the next step, helper 1's output stage): refresh what the env logic changed
+  if constexpr (ROLLOUT) {
+    // the LDS copy of the state is what comes next (the next step, a helper's output stage): refresh what the env logic changed
     if (do_reset) {
       L.s(S_POS + 0) = pos[0]; L.s(S_POS + 1) = m * pos[1]; L.s(S_POS + 2) = pos[2];
       L.s(S_QUAT + 0) = quat[0]; L.s(S_QUAT + 1) = m * quat[1]; L.s(S_QUAT + 2) = quat[2]; L.s(S_QUAT + 3) = m * quat[3];
@@ -966,9 +923,6 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     for (int i = 0; i < 3; ++i) { L.hs(kHandOut + 3 + i) = c.p[1][i]; L.hs(kHandOut + 8 + i) = c.p[2][i]; }
 #pragma unroll
     for (int i = 0; i < 2; ++i) { L.hs(kHandOut + 6 + i) = c.tilt[1][i]; L.hs(kHandOut + 11 + i) = c.tilt[2][i]; }
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (!ROLLOUT) __syncthreads();      // one launch per step: the helper emits NOW, beside this wavefront's env-level stores
-#endif
   } else {
     StepOut o;
 #pragma unroll
@@ -994,16 +948,16 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
       store_cache(P, e, c);
       store_headings(P, e, hd);
     }
-    gst<!ROLLOUT>(&Fo[F_POT * np], pot_prev);
-    gst<!ROLLOUT>(&Fo[F_ZINIT * np], z_init);
-    gst<!ROLLOUT>(&Fo[F_EPRET * np], ep_ret);
-    gst<!ROLLOUT>(&Fo[F_EPRET_LO * np], ep_lo);
-    gst<!ROLLOUT>(&Fo[F_NNDR * np], nn_dr);
-    gst<!ROLLOUT>(&P.istate[e + I_N * np], n);
-    gst<!ROLLOUT>(&P.istate[e + I_COUNT * np], count);
-    gst<!ROLLOUT>(&P.istate[e + I_ELAPSED * np], elapsed);
-    gst<!ROLLOUT>(&P.istate[e + I_RNG * np], (int)ctr);
-    gst<!ROLLOUT>(&P.istate[e + I_FLAGS * np], flags);
+    Fo[F_POT * np] = pot_prev;
+    Fo[F_ZINIT * np] = z_init;
+    Fo[F_EPRET * np] = ep_ret;
+    Fo[F_EPRET_LO * np] = ep_lo;
+    Fo[F_NNDR * np] = nn_dr;
+    P.istate[e + I_N * np] = n;
+    P.istate[e + I_COUNT * np] = count;
+    P.istate[e + I_ELAPSED * np] = elapsed;
+    P.istate[e + I_RNG * np] = (int)ctr;
+    P.istate[e + I_FLAGS * np] = flags;
   }
   SS_MEMBAR();
 #if defined(SS_PROFILE_PHASES) && defined(__HIP_DEVICE_COMPILE__)
@@ -1014,43 +968,11 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
 #endif
   }   // control steps of this launch
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (out_offload(HELPERS, ROLLOUT) && ROLLOUT) __syncthreads();   // a helper emits the last step's outputs
+  if constexpr (out_offload(HELPERS, ROLLOUT)) __syncthreads();   // a helper emits the last step's outputs
 #endif
 }
 
 #ifndef SS_HOST_HARNESS
-// Experiment (-DSS_CODE_PREFETCH=bytes, off by default): the helper wavefronts, idle until the main wavefront has loaded
-// the state, read the kernel's own code (from the entry point on) as data, so that the main wavefront's instruction fetches of a
-// launch's first control step find the lines in L2 instead of HBM / MALL (a kernel boundary invalidates the L2s of all eight XCDs).
-#if defined(SS_CODE_PREFETCH)
-__device__ __forceinline__ void prefetch_code(unsigned long long entry_pc, int helper, int nhelpers, int lane, uint32_t* sink) {
-  const uint4* p = reinterpret_cast<const uint4*>(entry_pc & ~63ull);
-  uint32_t acc = 0;
-#pragma unroll 4
-  for (int i = helper * kWave + lane; i < (SS_CODE_PREFETCH) / 16; i += nhelpers * kWave) { const uint4 v = p[i]; acc ^= v.x ^ v.w; }
-  if (acc == 0x9E3779B9u && sink) *sink = acc;       // (keeps the loads alive; practically never taken)
-}
-#define SS_PREFETCH_ENTRY() const unsigned long long entry_pc_ = __builtin_amdgcn_s_getpc()
-#define SS_PREFETCH(helper, n, lane) prefetch_code(entry_pc_, helper, n, lane, reinterpret_cast<uint32_t*>(P.prof))
-#else
-#define SS_PREFETCH_ENTRY() ((void)0)
-#define SS_PREFETCH(helper, n, lane) ((void)0)
-#endif
-// Layout experiment (-DSS_ENTRY_PAD=n / -DSS_HELPER_PAD=n: n `s_nop`s, 4 bytes each, executed once per launch at the kernel's entry /
-// at the head of the helper wavefronts' branch): the helped kernels are 77-85 KB of code against a 64 KB instruction cache shared by
-// two CUs, so where the main and the helper wavefronts' hot code falls in the cache is worth a few per cent.
-#define SS_STR2(x) #x
-#define SS_STR(x) SS_STR2(x)
-#if defined(SS_ENTRY_PAD) && defined(__HIP_DEVICE_COMPILE__)
-#define SS_PAD_ENTRY() asm volatile(".rept " SS_STR(SS_ENTRY_PAD) "\n s_nop 0\n .endr")
-#else
-#define SS_PAD_ENTRY() ((void)0)
-#endif
-#if defined(SS_HELPER_PAD) && defined(__HIP_DEVICE_COMPILE__)
-#define SS_PAD_HELPER() asm volatile(".rept " SS_STR(SS_HELPER_PAD) "\n s_nop 0\n .endr")
-#else
-#define SS_PAD_HELPER() ((void)0)
-#endif
 template <class Model, bool RANDOM_ACT>
 __global__ __launch_bounds__(kWave, 1) void step_kernel(Params P, StepIO io) {
   __shared__ float4 lds4[kLdsSlots * kWave];
@@ -1061,8 +983,6 @@ __global__ __launch_bounds__(kWave, 1) void step_kernel(Params P, StepIO io) {
 // helper_substep).  Worth it only while the batch leaves SIMDs idle (4096 envs occupy 128 of 1024).
 template <class Model, bool RANDOM_ACT, int HELPERS>
 __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void step_kernel_helped(Params P, StepIO io) {
-  SS_PREFETCH_ENTRY();
-  SS_PAD_ENTRY();
   __shared__ float4 lds4[(kLdsSlots + hand_slots(HELPERS)) * kWave];      // (three helpers: + the rows' own 40 words per lane)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & (kWave - 1);
   float* lds = reinterpret_cast<float*>(lds4);
@@ -1070,15 +990,9 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void step_kernel_helped(P
   if (wave == 0) {
     step_env<Model, RANDOM_ACT, HELPERS>(P, io, blockIdx.x * kWave + lane, lane, lds);
   } else {
-    SS_PREFETCH(wave - 1, HELPERS, lane);
-    SS_PAD_HELPER();
     const Lds L{lds, lane};
 #pragma unroll 1
-    for (int k = 0; k < SS_NUM_SUBSTEPS; ++k) helper_substep<Model, HELPERS>(wave - 1, L, [](int) {});
-    if constexpr (out_offload(HELPERS, false)) {     // (tuning option) the output stage on a helper, beside the main wavefront's own stores
-      __syncthreads();
-      if (wave == HELPERS) emit_from_handoff<Model, false>(P, io, L, lane, blockIdx.x * kWave + lane, 0, lds);
-    }
+    for (int k = 0; k < kNumSubsteps; ++k) helper_substep<Model, HELPERS, 6>(wave - 1, L, [](int) {});
   }
 }
 // K control steps per launch (ss_rollout_random): same code, state resident in LDS between the steps
@@ -1089,8 +1003,6 @@ __global__ __launch_bounds__(kWave, 1) void rollout_kernel(Params P, StepIO io) 
 }
 template <class Model, int HELPERS>
 __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helped(Params P, StepIO io) {
-  SS_PREFETCH_ENTRY();
-  SS_PAD_ENTRY();
   __shared__ float4 lds4[(kLdsSlots + hand_slots(HELPERS)) * kWave];      // (three helpers: + the rows' own 40 words per lane)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & (kWave - 1);
   float* lds = reinterpret_cast<float*>(lds4);
@@ -1098,8 +1010,6 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
   if (wave == 0) {
     step_env<Model, true, HELPERS, true>(P, io, blockIdx.x * kWave + lane, lane, lds);
   } else {
-    SS_PREFETCH(wave - 1, HELPERS, lane);
-    SS_PAD_HELPER();
     const Lds L{lds, lane};
     const int lane_global = blockIdx.x * kWave + lane, side = lane_global & 1;
     const int e = min(lane_global >> 1, P.n - 1);
@@ -1107,17 +1017,16 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
 #pragma unroll 1
     for (int kstep = 0; kstep < io.nsteps; ++kstep)
 #pragma unroll 1
-      for (int k = 0; k < SS_NUM_SUBSTEPS; ++k)
-        helper_substep<Model, HELPERS>(wave - 1, L, [&](int helper) {
+      for (int k = 0; k < kNumSubsteps; ++k)
+        helper_substep<Model, HELPERS, 4>(wave - 1, L, [&](int helper) {
           if (k != 0) return;
           SS_FUZZ(0x80u + helper);
           // the next control step's actions, while the main wavefront is in pass 1 / 2 of this step's first substep
           // (three helpers: helper 1 -- which also has the spine's bias forces in this window -- draws the actions, helper 2 has the
           // longer job, the previous step's outputs, to itself; rounds 3-5 had them the other way round)
-          constexpr int kActHelper = SS_EMIT_ON_LAST_HELPER && out_offload(HELPERS, true) ? 1 : HELPERS - 1;
-          constexpr int kEmitHelper = SS_EMIT_ON_LAST_HELPER && out_offload(HELPERS, true) ? HELPERS - 1 : 1;
+          constexpr int kActHelper = 1, kEmitHelper = HELPERS - 1;
           if (HELPERS > 1 && helper == kActHelper && kstep + 1 < io.nsteps)
-            random_actions_half<true>(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep + 1u, [&](int j, float a) { L.hs(kHandAct + j) = a; });
+            random_actions_half(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep + 1u, [&](int j, float a) { L.hs(kHandAct + j) = a; });
           // the previous control step's outputs
           if (out_offload(HELPERS, true) && helper == kEmitHelper && kstep > 0) emit_from_handoff<Model, true>(P, io, L, lane, lane_global, kstep - 1, lds);
         });
@@ -1128,43 +1037,7 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
     }
   }
 }
-#endif  // SS_HOST_HARNESS
 
-// (The non-template kernels of this header are `static`: the header is included by two translation units, ss_api.hip and
-// ss_rollout3.hip, and only ss_api.hip launches them.)
-// Consumer side of the peer-store all-gather: lane r waits until peer r has published `value` (or a later step) in this
-// rank's flag array.  Bounded spin: on time-out it raises *error instead of hanging the GPU.
-#ifndef SS_HOST_HARNESS
-static __global__ void peer_wait_kernel(const uint32_t* flags, int count, uint32_t value, uint32_t* error) {
-  const int r = threadIdx.x;
-  if (r >= count) return;
-  for (long long it = 0; it < (1ll << 23); ++it) {     // ~1 s
-    const uint32_t v = __hip_atomic_load(flags + r, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-    if ((int32_t)(v - value) >= 0) return;
-    __builtin_amdgcn_s_sleep(8);
-  }
-  *error = 1u + (uint32_t)r;
-}
-#endif
-
-// hook updates, stream-ordered (ss_api.hip)
-#ifndef SS_HOST_HARNESS
-static __global__ void set_knobs_kernel(Knobs* dst, Knobs v) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
-}
-// per-env sampling grids: [N][121] row-major (the caller's layout, playground/train.py:267-271) -> [121][Npad]
-static __global__ void transpose_prob_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int npad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * SS_NCELL) return;
-  const int e = i / SS_NCELL, k = i - e * SS_NCELL;
-  dst[(size_t)k * npad + e] = src[i];
-}
-static __global__ void copy_prob_kernel(const float* __restrict__ src, float* __restrict__ dst) {
-  if (threadIdx.x < SS_NCELL) dst[threadIdx.x] = src[threadIdx.x];
-}
-#endif
-
-#ifndef SS_HOST_HARNESS
 template <class Model>
 __global__ __launch_bounds__(kWave) void reset_kernel(Params P, float* obs) {
   const int e = blockIdx.x * kWave + threadIdx.x;
@@ -1196,9 +1069,7 @@ __global__ __launch_bounds__(kWave) void reset_kernel(Params P, float* obs) {
     for (int i = 0; i < SS_OBS_DIM; ++i) obs[(size_t)e * SS_OBS_DIM + i] = o[i];
   }
 }
-#endif  // SS_HOST_HARNESS
 
-#ifndef SS_HOST_HARNESS
 template <class Model>
 __global__ __launch_bounds__(kWave) void obs_kernel(Params P, float* obs) {
   const int e = blockIdx.x * kWave + threadIdx.x;
@@ -1214,108 +1085,6 @@ __global__ __launch_bounds__(kWave) void obs_kernel(Params P, float* obs) {
   for (int i = 0; i < SS_OBS_DIM; ++i) obs[(size_t)e * SS_OBS_DIM + i] = o[i];
 }
 #endif  // SS_HOST_HARNESS
-
-// one thread per (env, grid cell): PHYSICS.md section 8
-#ifndef SS_HOST_HARNESS
-// create_temp_states (common/envs_utils.py:573-578, playground/train.py:247-257): per env the 121 variants of the
-// current observation with the look-ahead stone moved to each (yaw, pitch) grid cell.  Only obs[55..59] differ:
-// obs_kernel first writes the current observation rows (lane per env, coalesced state loads) to a scratch [N,60];
-// then one 256-thread workgroup per env computes the 121 x 5 target features (one lane per cell) and streams the
-// [121,60] block out as 1815 coalesced float4 -- the one HBM-bound kernel of the path (29 KB written per env).
-#ifndef SS_TEMP_THREADS
-#define SS_TEMP_THREADS 240            // a multiple of 15: every thread keeps ONE float4 column of the row
-#endif
-constexpr int kTempThreads = SS_TEMP_THREADS;
-static __global__ __launch_bounds__(kTempThreads) void temp_states_kernel(Params P, const float* __restrict__ obs_rows, float* out) {
-  __shared__ __attribute__((aligned(16))) float base[SS_OBS_DIM];
-  __shared__ float feat[SS_NCELL * 5];
-  const int e = blockIdx.x, t = threadIdx.x;
-  const size_t np = (size_t)P.npad;
-  if (t < SS_OBS_DIM) base[t] = obs_rows[(size_t)e * SS_OBS_DIM + t];
-  if (t < SS_NCELL) {
-    const int cell = t;
-    float pos[3], quat[4], p1[3], p2[3], tilt2[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pos[i] = P.fstate[e + (F_POS + i) * np];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) quat[i] = P.fstate[e + (F_QUAT + i) * np];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { p1[i] = P.fstate[e + (F_STONE + 8 + i) * np]; p2[i] = P.fstate[e + (F_STONE + 16 + i) * np]; }
-    tilt2[0] = P.fstate[e + (F_STONE + 16 + 6) * np];
-    tilt2[1] = P.fstate[e + (F_STONE + 16 + 7) * np];
-    const int n = P.istate[e + I_N * np];
-    if (n + 1 <= kNumStones - 1) {
-      const float* T = P.terrain + e;
-      const float phi_n = n < P.istate[e + I_PROV * np] ? T[(n * 6 + 3) * np] : 0.f;      // a provisional stone is not stored
-      float phi = phi_n + yaw_sample(cell / SS_GRID), pitch = pitch_sample(cell % SS_GRID);
-      float dr = P.fstate[e + F_NNDR * np];
-      float sp, cp, sph, cph;
-      sincosf(pitch, &sp, &cp);
-      sincosf(phi, &sph, &cph);
-      float planar = dr * cp;
-      p2[0] = p1[0] + planar * cph;
-      p2[1] = p1[1] + planar * sph;
-      p2[2] = p1[2] + dr * sp;
-    }
-    float cyaw, syaw;                      // yaw only: (cos, sin) = (A, B) / |(A, B)| as in quat_roll_pitch_cs
-    {
-      const float A = 1.f - 2.f * (quat[2] * quat[2] + quat[3] * quat[3]), B = 2.f * (quat[0] * quat[3] + quat[1] * quat[2]);
-      const float n2 = A * A + B * B, inv = rsqrtf(fmaxf(n2, 1e-30f));
-      cyaw = n2 > 1e-30f ? A * inv : 1.f;
-      syaw = n2 > 1e-30f ? B * inv : 0.f;
-    }
-    float f[5];
-    target_features(pos, cyaw, syaw, p2, tilt2, f);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) feat[cell * 5 + i] = f[i];
-  }
-  __syncthreads();
-  // Measured in round 2 (profiles/r02_*_temp_states.txt): this one-workgroup-per-env shape writes 5.0-5.3 TB/s at 32768
-  // envs (a torch fill of the same buffer: 6.9 TB/s) -- and it stays there with the feature computation removed, with 60-
-  // or 120-thread workgroups, with persistent workgroups (4.1-5.0 TB/s) and with one workgroup per 16 rows (1.8 TB/s,
-  // latency-bound): the limit is the write pattern of 29,040-byte blocks, not the prologue.
-  constexpr int kRow4 = SS_OBS_DIM / 4;                      // 15 float4 per row
-  static_assert(kTempThreads % kRow4 == 0, "a thread must stay in its column");
-  constexpr int kRowsPerPass = kTempThreads / kRow4;
-  float4* o4 = reinterpret_cast<float4*>(out) + (size_t)e * (SS_NCELL * kRow4);
-  const float4* b4 = reinterpret_cast<const float4*>(base);
-  const int c4 = t % kRow4;
-  const float4 bv = b4[c4 < kRow4 - 1 ? c4 : kRow4 - 2];     // this thread's column of the common part, in registers
-#pragma unroll 1
-  for (int row = t / kRow4; row < SS_NCELL; row += kRowsPerPass) {
-    float4 v = bv;
-    const float* f = feat + row * 5;
-    if (c4 == kRow4 - 2) v.w = f[0];                         // obs[52..54], obs[55]
-    if (c4 == kRow4 - 1) v = make_float4(f[1], f[2], f[3], f[4]);
-    o4[row * kRow4 + c4] = v;          // plain stores: nontemporal ones measured 20 % slower here
-  }
-}
-#endif  // SS_HOST_HARNESS
-
-#ifndef SS_HOST_HARNESS
-static __global__ void random_actions_kernel(Params P, uint64_t t, float* act) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= P.n) return;
-#pragma unroll
-  for (int b = 0; b < 6; ++b) {
-    uint32_t r[4];
-    philox4x32_10((uint32_t)(6u * (uint32_t)t + b), 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, r);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int j = b * 4 + i;
-      if (j < NJ) act[(size_t)e * NJ + j] = 2.f * u01(r[i]) - 1.f;
-    }
-  }
-}
-#endif  // SS_HOST_HARNESS
-
-#ifndef SS_HOST_HARNESS
-// PMC calibration: a dword-per-lane coalesced copy with the step kernel's access shape (tools/hbm_traffic.py)
-static __global__ void calib_copy_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[i] + 1.0f;
-}
-#endif
 
 // packed [N,186] <-> structure of arrays (PHYSICS / include/steppingstone.h layout)
 SSD void pack_env(const Params& P, int e, float* packed) {
@@ -1355,17 +1124,5 @@ SSD void unpack_env(const Params& P, int e, const float* packed) {
   store_cache(P, e, c);
   store_headings(P, e, hd);
 }
-#ifndef SS_HOST_HARNESS
-static __global__ void pack_state_kernel(Params P, float* packed) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < P.n) pack_env(P, e, packed);
-}
-#endif  // SS_HOST_HARNESS
-#ifndef SS_HOST_HARNESS
-static __global__ void unpack_state_kernel(Params P, const float* packed) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < P.n) unpack_env(P, e, packed);
-}
-#endif  // SS_HOST_HARNESS
 
 }  // namespace ss

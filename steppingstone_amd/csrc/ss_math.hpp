@@ -16,29 +16,16 @@
 #define SSD __host__ __device__ __forceinline__
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// optional scheduling fence between links of the unrolled tree sweeps (-DSS_SCHED_FENCE): measured round 1, it
-// lowers spills slightly (1325 -> 1193) but costs 4 % of step time, so it is off by default
-#if defined(SS_SCHED_FENCE)
-#define SS_FENCE() __builtin_amdgcn_sched_barrier(0)
-#elif defined(SS_MEM_FENCE)
-#define SS_FENCE() asm volatile("" ::: "memory")
-#else
-#define SS_FENCE() ((void)0)
-#endif
 // hides a value from CSE so that address arithmetic is redone after a long region instead of being kept live
 #define SS_OPAQUE(x) asm volatile("" : "+v"(x))
 #define SS_RSQRT(x) rsqrtf(x)
 // reciprocal: v_rcp_f32 (1 ulp) + one Newton step = 3 VALU instructions where the IEEE division expands to ~10
-// (24 of them per substep: joint 1/D and contact-row 1/A).  -DSS_IEEE_DIV restores the division.
-#ifdef SS_IEEE_DIV
-#define SS_RCP(x) (1.0f / (x))
-#else
+// (24 of them per substep: joint 1/D and contact-row 1/A)
 static __device__ __forceinline__ float ss_rcp(float x) {
   float r = __builtin_amdgcn_rcpf(x);
   return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
 }
 #define SS_RCP(x) ss_rcp(x)
-#endif
 #define SS_UMULHI(a, b) __umulhi((a), (b))
 #define SS_F2U(x) __float_as_uint(x)
 #else
@@ -49,7 +36,6 @@ void ss_host_wave_sync();      // barrier over the 64 lane threads of a wavefron
 static inline float ss_host_rsqrt(float x) { return 1.0f / sqrtf(x); }
 static inline unsigned ss_host_umulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
 static inline unsigned ss_host_f2u(float x) { unsigned u; std::memcpy(&u, &x, 4); return u; }
-#define SS_FENCE() ((void)0)
 #define SS_OPAQUE(x) asm volatile("" : "+r"(x))
 #define SS_RSQRT(x) ss_host_rsqrt(x)
 #define SS_RCP(x) (1.0f / (x))
