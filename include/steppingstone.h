@@ -36,8 +36,9 @@ extern "C" {
 #define SS_INFO_WORDS 6    /* 32-bit words of ss_info */
 #define SS_ABI_VERSION 4   /* ss_version(): 2 -> 3 added ss_info.ep_ret_lo and state word 185 (round 3); 3 -> 4 (round 4) changed a
                             * MEANING, no layout: actions and observations carry POLICY coordinates, see "Joint conventions".
-                            * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) were ADDED under
-                            * version 4: no existing layout or meaning changed, so a version-4 binding keeps working. */
+                            * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) and the per-env
+                            * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
+                            * existing layout or meaning changed, so a version-4 binding keeps working. */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -145,7 +146,8 @@ int ss_set_sample_prob_device(ss_env* env, const float* prob, int per_env, void*
 int ss_set_mirror(ss_env* env, int32_t on);
 int ss_set_power(ss_env* env, float power);                     /* env.set_robot_params({"power": p}) */
 /* on (default): worker semantics, a finished env is reset inside the step (envs_utils.py:647-648);
- * off: plain gym env semantics for make_env() users -- terminal obs returned, caller resets (train.py:243-244). */
+ * off: plain gym env semantics for make_env() users -- terminal obs returned, caller resets (train.py:243-244); a batch resets its
+ * finished envs with ss_reset_masked. */
 int ss_set_auto_reset(ss_env* env, int32_t on);
 
 /* env.create_temp_states (train.py:247, envs_utils.py:573-578): out [N,121,60] f32, device pointer. */
@@ -167,6 +169,28 @@ int ss_get_state(ss_env* env, float* packed, void* stream);
 int ss_set_state(ss_env* env, const float* packed, void* stream);
 /* Observation of the current state without stepping (used after ss_set_state). */
 int ss_get_obs(ss_env* env, float* obs, void* stream);
+
+/* Per-env episode control: the reference resets each env in its own worker process (common/envs_utils.py:642-649); these reset or
+ * move a subset of the batch.  Added under version 4 (no existing layout or meaning changed).  All three are ordered on `stream`,
+ * never synchronise the host, allocate nothing and can be captured into a hipGraph.  Bad host-side arguments return SS_ERR_INVALID
+ * and launch nothing.
+ *
+ * ss_reset_masked: resets env e iff mask[e] != 0 (mask: DEVICE [N] u8; the done output of ss_step is a valid mask), the reset of
+ * ss_reset.  obs (may be NULL: state only) receives the fresh observation in row e, with a row stride of obs_stride floats: 60 for
+ * ss_step's [N,60] obs, 62 for ss_step_packed's [N,62] block (its rew / done words are left alone).  terminal_obs (optional, DEVICE
+ * [N,60], needs obs): row e receives row e of obs as it was BEFORE the reset, i.e. the terminal observation of a finished step.
+ * An env with mask[e] == 0 is not touched: no state word, obs row or terminal row is read or written.  With auto-reset off, ss_step
+ * followed by ss_reset_masked(done) leaves exactly the state, obs, rew, done and info of ss_step with auto-reset on.
+ * obs_stride must be 60 or 62.
+ *
+ * ss_get_state_envs / ss_set_state_envs: ss_get_state / ss_set_state for the m envs listed in env_ids (DEVICE [m] int32): row k of
+ * packed ([m, SS_STATE_DIM] f32, the layout above) <-> env env_ids[k].  m >= 0 (0: nothing happens); env_ids and packed may be NULL
+ * only when m == 0.  An id outside [0, N) lives on the device and is not checked here: it is skipped (no row read or written).
+ * Duplicate ids in ss_set_state_envs: which row lands in that env is unspecified (the words may even mix rows); callers pass
+ * distinct ids. */
+int ss_reset_masked(ss_env* env, const uint8_t* mask, float* obs, int32_t obs_stride, float* terminal_obs, void* stream);
+int ss_get_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, float* packed, void* stream);
+int ss_set_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, const float* packed, void* stream);
 
 int32_t ss_num_envs(const ss_env* env);
 /* SS_ABI_VERSION of the library.  A binding must check it at load time (steppingstone_amd/_lib.py does): version 2 inserted

@@ -20,7 +20,7 @@ SYMBOLS = [
     "ss_version", "ss_set_sample_prob_device", "ss_debug_calib_copy", "ss_debug_phase_cycles",
     "ss_peer_alloc", "ss_peer_free", "ss_peer_ipc_handle", "ss_peer_ipc_open", "ss_peer_ipc_close", "ss_peer_connect",
     "ss_step_packed_peers", "ss_peer_wait", "ss_peer_error", "ss_rollout_random_packed", "ss_debug_set_id_mask",
-    "ss_camera_default", "ss_body_poses", "ss_render",
+    "ss_camera_default", "ss_body_poses", "ss_render", "ss_reset_masked", "ss_get_state_envs", "ss_set_state_envs",
 ]
 NUM_BODIES = 22           # torso + 21 links: ss_body_poses rows per env
 CAM_TRACK, CAM_CHASE, CAM_FIXED = 0, 1, 2     # ss_camera.mode
@@ -85,6 +85,9 @@ def load():
     lib.ss_get_state.argtypes = [vp, vp, vp]
     lib.ss_set_state.argtypes = [vp, vp, vp]
     lib.ss_get_obs.argtypes = [vp, vp, vp]
+    lib.ss_reset_masked.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.ss_get_state_envs.argtypes = [vp, vp, i32, vp, vp]
+    lib.ss_set_state_envs.argtypes = [vp, vp, i32, vp, vp]
     lib.ss_num_envs.argtypes = [vp]
     lib.ss_num_envs.restype = i32
     lib.ss_version.restype = C.c_int

@@ -154,6 +154,40 @@ static __global__ void unpack_state_kernel(Params P, const float* packed) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < P.n) unpack_env(P, e, packed);
 }
+// packed row k <-> env ids[k] (ss_get_state_envs / ss_set_state_envs).  The ids live on the device and are not checked by the host:
+// an id outside [0, N) is skipped -- its row is neither read nor written (the rule of ss_render)
+static __global__ void pack_state_ids_kernel(Params P, const int32_t* ids, int m, float* packed) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= m) return;
+  const int e = ids[k];
+  if (e >= 0 && e < P.n) pack_env(P, e, packed, (size_t)k);
+}
+static __global__ void unpack_state_ids_kernel(Params P, const int32_t* ids, int m, const float* packed) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= m) return;
+  const int e = ids[k];
+  if (e >= 0 && e < P.n) unpack_env(P, e, packed, (size_t)k);
+}
+
+// Reset of the envs whose mask byte is set (ss_reset_masked), one lane per env like reset_kernel.  With auto-reset off, a step
+// followed by this kernel with the step's done as the mask leaves the state and outputs of a step with auto-reset on: both resets
+// draw from the env's own Philox counter as it stands after the step.  An env whose byte is 0 is not touched at all (no state
+// word, obs row or terminal row read or written), and a wavefront without a masked env ends after its 64 mask bytes.
+template <class Model>
+static __global__ __launch_bounds__(kWave) void reset_masked_kernel(Params P, const uint8_t* mask, float* obs, int obs_stride,
+                                                                    float* terminal_obs) {
+  const int e = blockIdx.x * kWave + threadIdx.x;
+  if (e >= P.n || mask[e] == 0) return;
+  float* row = obs ? obs + (size_t)e * obs_stride : nullptr;
+  if (terminal_obs) {                  // the observation the finished step left, before the fresh one replaces it
+    float t[SS_OBS_DIM];
+#pragma unroll
+    for (int i = 0; i < SS_OBS_DIM; ++i) t[i] = row[i];
+#pragma unroll
+    for (int i = 0; i < SS_OBS_DIM; ++i) terminal_obs[(size_t)e * SS_OBS_DIM + i] = t[i];
+  }
+  reset_env<Model>(P, e, row);
+}
 
 }  // namespace ss
 
@@ -665,6 +699,46 @@ int ss_set_state(ss_env* env, const float* packed, void* stream) {
   if (!env || !packed) return fail(SS_ERR_INVALID, "null argument");
   SS_HIP(hipSetDevice(env->device));
   hipLaunchKernelGGL(ss::unpack_state_kernel, dim3((env->P.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, packed);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+int ss_reset_masked(ss_env* env, const uint8_t* mask, float* obs, int32_t obs_stride, float* terminal_obs, void* stream) {
+  if (!env || !mask) return fail(SS_ERR_INVALID, "null handle or mask");
+  if (obs_stride != SS_OBS_DIM && obs_stride != SS_OBS_DIM + 2)
+    return fail(SS_ERR_INVALID, "ss_reset_masked: obs_stride must be 60 (ss_step's obs) or 62 (ss_step_packed's block)");
+  if (terminal_obs && !obs) return fail(SS_ERR_INVALID, "ss_reset_masked: terminal_obs needs obs to copy the rows from");
+  SS_HIP(hipSetDevice(env->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (env->kind == SS_WALKER3D)
+    hipLaunchKernelGGL((ss::reset_masked_kernel<ss::ModelWalker3D>), grid64(env), dim3(ss::kWave), 0, st, env->P, mask, obs,
+                       (int)obs_stride, terminal_obs);
+  else
+    hipLaunchKernelGGL((ss::reset_masked_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, st, env->P, mask, obs,
+                       (int)obs_stride, terminal_obs);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+int ss_get_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, float* packed, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_get_state_envs: m must be >= 0");
+  if (m > 0 && (!env_ids || !packed)) return fail(SS_ERR_INVALID, "ss_get_state_envs: env_ids and packed must be device pointers");
+  if (m == 0) return SS_OK;
+  SS_HIP(hipSetDevice(env->device));
+  hipLaunchKernelGGL(ss::pack_state_ids_kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, env_ids, (int)m, packed);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+int ss_set_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, const float* packed, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_set_state_envs: m must be >= 0");
+  if (m > 0 && (!env_ids || !packed)) return fail(SS_ERR_INVALID, "ss_set_state_envs: env_ids and packed must be device pointers");
+  if (m == 0) return SS_OK;
+  SS_HIP(hipSetDevice(env->device));
+  hipLaunchKernelGGL(ss::unpack_state_ids_kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, env_ids, (int)m,
+                     packed);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }

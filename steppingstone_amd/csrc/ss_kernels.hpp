@@ -1038,10 +1038,10 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
   }
 }
 
+// Reset of env e and its stores (reset_kernel, and reset_masked_kernel in ss_api.hip): the state the step kernel's in-place reset
+// leaves, from the same Philox counter; the fresh observation goes to obs_row[0..59] unless obs_row is null.
 template <class Model>
-__global__ __launch_bounds__(kWave) void reset_kernel(Params P, float* obs) {
-  const int e = blockIdx.x * kWave + threadIdx.x;
-  if (e >= P.n) return;
+SSD void reset_env(const Params& P, int e, float* obs_row) {
   const size_t np = (size_t)P.npad;
   Dyn s;
   Cache c;
@@ -1062,12 +1062,19 @@ __global__ __launch_bounds__(kWave) void reset_kernel(Params P, float* obs) {
   P.istate[e + I_ELAPSED * np] = 0;
   P.istate[e + I_RNG * np] = (int)ctr;
   P.istate[e + I_FLAGS * np] = 0;
-  if (obs) {
+  if (obs_row) {
     float o[SS_OBS_DIM];
     write_obs<Model>(s, z_init, 0, c, o);
 #pragma unroll
-    for (int i = 0; i < SS_OBS_DIM; ++i) obs[(size_t)e * SS_OBS_DIM + i] = o[i];
+    for (int i = 0; i < SS_OBS_DIM; ++i) obs_row[i] = o[i];
   }
+}
+
+template <class Model>
+__global__ __launch_bounds__(kWave) void reset_kernel(Params P, float* obs) {
+  const int e = blockIdx.x * kWave + threadIdx.x;
+  if (e >= P.n) return;
+  reset_env<Model>(P, e, obs ? obs + (size_t)e * SS_OBS_DIM : nullptr);
 }
 
 template <class Model>
@@ -1086,10 +1093,11 @@ __global__ __launch_bounds__(kWave) void obs_kernel(Params P, float* obs) {
 }
 #endif  // SS_HOST_HARNESS
 
-// packed [N,186] <-> structure of arrays (PHYSICS / include/steppingstone.h layout)
-SSD void pack_env(const Params& P, int e, float* packed) {
+// packed [N,186] <-> structure of arrays (PHYSICS / include/steppingstone.h layout): env e <-> row `row` of packed (the whole-batch
+// forms: row e; ss_get_state_envs / ss_set_state_envs: row k <-> env ids[k])
+SSD void pack_env(const Params& P, int e, float* packed, size_t row) {
   const size_t np = (size_t)P.npad;
-  float* o = packed + (size_t)e * SS_STATE_DIM;
+  float* o = packed + row * SS_STATE_DIM;
   for (int i = 0; i < 59; ++i) o[i] = P.fstate[e + (size_t)i * np];
   o[59] = (float)P.istate[e + I_N * np];
   o[60] = (float)P.istate[e + I_COUNT * np];
@@ -1105,9 +1113,10 @@ SSD void pack_env(const Params& P, int e, float* packed) {
   }
   o[185] = P.fstate[e + (size_t)F_EPRET_LO * np];
 }
-SSD void unpack_env(const Params& P, int e, const float* packed) {
+SSD void pack_env(const Params& P, int e, float* packed) { pack_env(P, e, packed, (size_t)e); }
+SSD void unpack_env(const Params& P, int e, const float* packed, size_t row) {
   const size_t np = (size_t)P.npad;
-  const float* o = packed + (size_t)e * SS_STATE_DIM;
+  const float* o = packed + row * SS_STATE_DIM;
   for (int i = 0; i < 59; ++i) P.fstate[e + (size_t)i * np] = o[i];
   int n = (int)o[59];
   P.istate[e + I_N * np] = n;
@@ -1124,5 +1133,6 @@ SSD void unpack_env(const Params& P, int e, const float* packed) {
   store_cache(P, e, c);
   store_headings(P, e, hd);
 }
+SSD void unpack_env(const Params& P, int e, const float* packed) { unpack_env(P, e, packed, (size_t)e); }
 
 }  // namespace ss

@@ -151,6 +151,19 @@ class HipBackend:
     def get_obs(self, obs):
         _lib.check(self.lib.ss_get_obs(self.h, _ptr(obs), _stream(self.device)))
 
+    def reset_masked(self, mask, obs, terminal=None):
+        """mask: uint8 device tensor [N]; obs: None, [N,60] or the [N,62] packed block; terminal: None or [N,60]."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        stride = OBS_DIM if obs is None else int(obs.stride(0))
+        _lib.check(self.lib.ss_reset_masked(self.h, _ptr(mask), opt(obs), stride, opt(terminal), _stream(self.device)))
+
+    def get_state_envs(self, env_ids, packed):
+        """env_ids: int32 device tensor [M] of checked ids; packed: [M,186]."""
+        _lib.check(self.lib.ss_get_state_envs(self.h, _ptr(env_ids), int(env_ids.numel()), _ptr(packed), _stream(self.device)))
+
+    def set_state_envs(self, env_ids, packed):
+        _lib.check(self.lib.ss_set_state_envs(self.h, _ptr(env_ids), int(env_ids.numel()), _ptr(packed), _stream(self.device)))
+
     def body_poses(self, out):
         _lib.check(self.lib.ss_body_poses(self.h, _ptr(out), _stream(self.device)))
 
@@ -188,11 +201,17 @@ class SteppingStoneVecEnv:
     rews float64 (N,), dones bool (N,), infos sequence of N dicts; common/envs_utils.py:555-558) so that
     playground/train.py consumes it unchanged; return_numpy=False keeps everything on the GPU (obs/rew/done
     tensors, infos as a dict of tensors) for a device-resident PPO loop.
+
+    keep_terminal_obs=True keeps auto-reset's results bit for bit and also returns the observation each finished env ended in:
+    the kernel steps with its auto-reset off and ss_reset_masked resets the finished envs behind it on the same stream, copying
+    their rows out first.  Tensor mode: info["terminal_obs"] [N,60] (rows where done is set are meaningful); numpy mode:
+    infos[i]["terminal_observation"], a float32 (60,) array, for the finished envs only (the gymnasium / Stable-Baselines3 keys).
     """
 
     closed = False
 
-    def __init__(self, env_id, num_envs, seed=0, device=None, env_id_offset=0, return_numpy=False, backend=None, log_dir=None):
+    def __init__(self, env_id, num_envs, seed=0, device=None, env_id_offset=0, return_numpy=False, backend=None, log_dir=None,
+                 keep_terminal_obs=False):
         self.env_id = env_id
         self.kind = kind_of(env_id)
         self.num_envs = int(num_envs)
@@ -222,6 +241,11 @@ class SteppingStoneVecEnv:
                             "dev": torch.zeros((n, OBS_DIM + 2), dtype=torch.float32, device=dev),
                             "info": torch.zeros((n, INFO_WORDS), dtype=torch.int32).pin_memory(),
                             "event": torch.cuda.Event()}
+        self.keep_terminal_obs = bool(keep_terminal_obs)
+        self._terminal = None
+        if self.keep_terminal_obs:
+            self.backend.set_auto_reset(False)       # step() / step_packed() reset the finished envs behind each step
+            self._terminal = torch.zeros((n, OBS_DIM), dtype=torch.float32, device=dev)
         self._tstart = time.time()
         # Monitor's files (common/envs_utils.py:36-38,172-194): <log_dir>/<rank>.monitor.csv per env, a row per finished episode
         self._monitor = None
@@ -236,12 +260,44 @@ class SteppingStoneVecEnv:
         self.curriculum = 0
 
     # ------------------------------------------------------------------ gym / VecEnv protocol
-    def reset(self):
+    def reset(self, env_ids=None):
+        """Reset all envs (env_ids=None) and return their observations [N,60], or reset only the envs env_ids names:
+          * a host int sequence / ndarray, or an int tensor (checked on the host: one sync for a device tensor) -- returns the
+            fresh observations of those envs as [m,60], rows in env_ids order;
+          * a mask: a bool or uint8 tensor of shape [N] (e.g. the done of step()) -- never read on the host, so the call does not
+            synchronise and can be captured into a graph; returns the [N,60] observations of all envs, the masked rows fresh.
+        Out-of-range or duplicate ids and a mask of the wrong shape raise ValueError before anything runs on the GPU.  The env's own
+        obs buffer (the tensor step() returns in tensor mode) gets the fresh rows in place.  A reset env starts a new episode from its
+        own random stream, exactly as an auto-reset inside step() would.  Resetting an env in mid-episode writes no Monitor row: the
+        dropped episode is not reported, as in the reference, where it never finishes."""
         if self._pending:
             print("Called reset() while waiting for the step to complete")
             self.step_wait()
-        self.backend.reset(self._obs)
-        return self._out_obs()
+        if env_ids is None:
+            self.backend.reset(self._obs)
+            return self._out_obs()
+        mask, ids = self._env_ids(env_ids, allow_mask=True)
+        if mask is not None:
+            self.backend.reset_masked(mask, self._obs)
+            return self._out_obs()
+        dev_ids = torch.from_numpy(ids).to(self.device)
+        if ids.size:
+            m = np.zeros(self.num_envs, np.uint8)
+            m[ids] = 1
+            self.backend.reset_masked(torch.from_numpy(m).to(self.device), self._obs)
+        rows = self._obs.index_select(0, dev_ids)
+        return rows.cpu().numpy() if self.return_numpy else rows
+
+    def set_auto_reset(self, on):
+        """on (default): an env that finishes is reset inside step() (the reference's worker, common/envs_utils.py:646-649).  off:
+        step() returns the terminal observation of a finished env, which stays finished until reset(done) (or reset(ids)) resets it.
+        With keep_terminal_obs=True the envs already reset themselves and return the terminal rows: turning it off raises ValueError."""
+        if self.keep_terminal_obs:
+            if not on:
+                raise ValueError("set_auto_reset(False) on an env made with keep_terminal_obs=True: that env resets its finished envs "
+                                 "itself; make it with keep_terminal_obs=False to reset them with reset(done)")
+            return
+        self.backend.set_auto_reset(bool(on))
 
     def step_async(self, actions):
         if self._pinned is not None and not torch.is_tensor(actions):
@@ -251,6 +307,9 @@ class SteppingStoneVecEnv:
             pb["act"].numpy()[...] = a.reshape(self.num_envs, ACT_DIM)
             self._act.copy_(pb["act"], non_blocking=True)
             self.backend.step_packed(self._act, False, 0, pb["dev"], self._info)
+            if self.keep_terminal_obs:
+                self._done.copy_(pb["dev"][:, OBS_DIM + 1])          # the block's done column (0 / 1) as the u8 mask
+                self.backend.reset_masked(self._done, pb["dev"], self._terminal)
             pb["out"].copy_(pb["dev"], non_blocking=True)
             pb["info"].copy_(self._info, non_blocking=True)      # the step report travels with the block: no second, synchronous copy
             pb["event"].record()
@@ -263,6 +322,8 @@ class SteppingStoneVecEnv:
         assert a.shape[0] == self.num_envs, "expected %d actions, got %d" % (self.num_envs, a.shape[0])
         self._act.copy_(a.reshape(self.num_envs, ACT_DIM))
         self.backend.step(self._act, self._obs, self._rew, self._done, self._info)
+        if self.keep_terminal_obs:
+            self.backend.reset_masked(self._done, self._obs, self._terminal)
         self._pending = True
 
     def step_wait(self):
@@ -275,17 +336,31 @@ class SteppingStoneVecEnv:
             rew = out[:, OBS_DIM].astype(np.float64)
             done = out[:, OBS_DIM + 1] > 0.5
             self._info_host = pb["info"].numpy()
-            return obs, rew, done, self._info_dicts(done, self._info_host)
+            return obs, rew, done, self._terminal_infos(done, self._info_dicts(done, self._info_host))
         self._pending = False
         if not self.return_numpy:
             if self._monitor is not None:      # opt-in (log_dir): the episode rows need the finished envs on the host every step
                 self._info_dicts(self._done.cpu().numpy().astype(bool))
-            return self._obs, self._rew, self._done.bool(), self._info_tensors()
+            info = self._info_tensors()
+            if self.keep_terminal_obs:
+                info["terminal_obs"] = self._terminal
+            return self._obs, self._rew, self._done.bool(), info
         obs = self._obs.cpu().numpy()
         rew = self._rew.cpu().numpy().astype(np.float64)
         done = self._done.cpu().numpy().astype(bool)
         self._info_host = self._info.cpu().numpy()
-        return obs, rew, done, self._info_dicts(done, self._info_host)
+        return obs, rew, done, self._terminal_infos(done, self._info_dicts(done, self._info_host))
+
+    def _terminal_infos(self, done, infos):
+        """keep_terminal_obs, numpy mode: infos[i]["terminal_observation"] for the finished envs; their rows travel to the host in
+        steps where an env finished only."""
+        idx = np.nonzero(done)[0]
+        if not self.keep_terminal_obs or not idx.size:
+            return infos
+        rows = self._terminal.index_select(0, torch.from_numpy(idx).to(self.device)).cpu().numpy()
+        for k, i in enumerate(idx.tolist()):
+            infos[i]["terminal_observation"] = rows[k]
+        return infos
 
     def step(self, actions):
         self.step_async(actions)
@@ -294,25 +369,36 @@ class SteppingStoneVecEnv:
     def rollout_random(self, num_steps, t0=0, steps_per_launch=0):
         """BASELINE metric path: num_steps control steps with on-device U(-1,1) actions (Philox stream 1),
         steps_per_launch of them per kernel launch (0: the library default of 1000; 1: one launch per step)."""
+        self._no_multi_step()
         self.backend.rollout_random(num_steps, t0, self._obs, self._rew, self._done, self._info, steps_per_launch)
         return self._obs, self._rew, self._done
 
     def step_packed(self, packed, actions=None, t=0, info=None):
         """One step written into the caller's [N,62] buffer (obs | rew | done): the block ShardedVecEnv all-gathers.
         actions=None draws them from the benchmark Philox stream at index t.  info: optional caller-owned [N,5] int32
-        buffer for the per-env step report (default: this env's own)."""
+        buffer for the per-env step report (default: this env's own).  keep_terminal_obs: the finished envs are reset into the
+        block behind the step (their terminal rows: self._terminal)."""
         if actions is not None:
             self._act.copy_(actions.reshape(self.num_envs, ACT_DIM))
         self.backend.step_packed(self._act if actions is not None else None, actions is None, t, packed,
                                  self._info if info is None else info)
+        if self.keep_terminal_obs:
+            self._done.copy_(packed[:, OBS_DIM + 1])
+            self.backend.reset_masked(self._done, packed, self._terminal)
         return packed
 
     def rollout_random_packed(self, packed, t0=0):
         """packed: [K, N, 62] device buffer; ONE launch advances K control steps and writes step k's obs | rew | done block at
         packed[k] (the multi-GPU rollout ships such a chunk per collective)."""
         assert packed.dim() == 3 and packed.shape[1] == self.num_envs and packed.shape[2] == OBS_DIM + 2 and packed.is_contiguous()
+        self._no_multi_step()
         self.backend.rollout_random_packed(packed.shape[0], t0, packed, self._info)
         return packed
+
+    def _no_multi_step(self):
+        if self.keep_terminal_obs:
+            raise ValueError("keep_terminal_obs=True resets the finished envs behind each step; a multi-step rollout launch has no "
+                             "place for that: use step() / step_packed(), or an env made with keep_terminal_obs=False")
 
     def random_actions(self, t):
         self.backend.random_actions(t, self._act)
@@ -440,14 +526,32 @@ class SteppingStoneVecEnv:
         return _lib.mirror_indices(self.kind)
 
     # ------------------------------------------------------------------ state access
-    def get_state(self):
-        st = torch.empty((self.num_envs, STATE_DIM), dtype=torch.float32, device=self.device)
-        self.backend.get_state(st)
+    def get_state(self, env_ids=None):
+        """Packed state [N,186] (include/steppingstone.h), or [m,186] of the envs env_ids names (the forms of reset(); a mask here
+        selects its envs in ascending order), rows in env_ids order."""
+        if env_ids is None:
+            st = torch.empty((self.num_envs, STATE_DIM), dtype=torch.float32, device=self.device)
+            self.backend.get_state(st)
+            return st
+        _, ids = self._env_ids(env_ids, allow_mask=False)
+        st = torch.empty((ids.size, STATE_DIM), dtype=torch.float32, device=self.device)
+        if ids.size:
+            self.backend.get_state_envs(torch.from_numpy(ids.astype(np.int32)).to(self.device), st)
         return st
 
-    def set_state(self, packed):
-        st = torch.as_tensor(packed, dtype=torch.float32).to(self.device).contiguous().reshape(self.num_envs, STATE_DIM)
-        self.backend.set_state(st)
+    def set_state(self, packed, env_ids=None):
+        """Inject the packed state of all envs ([N,186]), or of the envs env_ids names ([m,186], row k -> env env_ids[k]; ids checked
+        as in reset(), duplicates rejected)."""
+        if env_ids is None:
+            st = torch.as_tensor(packed, dtype=torch.float32).to(self.device).contiguous().reshape(self.num_envs, STATE_DIM)
+            self.backend.set_state(st)
+            return
+        _, ids = self._env_ids(env_ids, allow_mask=False)
+        st = torch.as_tensor(packed, dtype=torch.float32).to(self.device).contiguous()
+        if st.numel() != ids.size * STATE_DIM:
+            raise ValueError("set_state: %d env ids need packed of shape (%d, %d), got %s" % (ids.size, ids.size, STATE_DIM, tuple(st.shape)))
+        if ids.size:
+            self.backend.set_state_envs(torch.from_numpy(ids.astype(np.int32)).to(self.device), st.reshape(ids.size, STATE_DIM))
 
     def get_obs(self):
         self.backend.get_obs(self._obs)
@@ -463,6 +567,31 @@ class SteppingStoneVecEnv:
         return self.get_state()[:, 59].cpu().numpy().astype(np.int64)
 
     # ------------------------------------------------------------------ helpers
+    def _env_ids(self, env_ids, allow_mask):
+        """Check env_ids on the host before anything indexes with them on the GPU (a device-side index assert is a GPU fault).
+        Returns (mask, None) for a bool / uint8 TENSOR of shape [N] when allow_mask (uint8 on the env's device, never read here), else
+        (None, ids): a host int64 array of distinct ids in [0, N) (a mask, a numpy bool array included, gives its set envs in order)."""
+        n = self.num_envs
+        if torch.is_tensor(env_ids) and env_ids.dtype in (torch.bool, torch.uint8) or isinstance(env_ids, np.ndarray) and env_ids.dtype == bool:
+            if tuple(env_ids.shape) != (n,):
+                raise ValueError("an env mask must have shape (%d,), got %s" % (n, tuple(env_ids.shape)))
+            if allow_mask and torch.is_tensor(env_ids):
+                mask = env_ids.to(self.device).contiguous()
+                return (mask.view(torch.uint8) if mask.dtype == torch.bool else mask), None
+            mask = env_ids.cpu().numpy() if torch.is_tensor(env_ids) else env_ids
+            return None, np.nonzero(mask)[0].astype(np.int64)
+        ids = env_ids.detach().cpu().numpy() if torch.is_tensor(env_ids) else np.asarray(env_ids)    # (a device tensor: one sync)
+        if ids.size == 0:
+            return None, np.zeros(0, np.int64)
+        if ids.ndim > 1 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("env ids must be a one-dimensional sequence of integers, got dtype %s shape %s" % (ids.dtype, ids.shape))
+        ids = ids.reshape(-1).astype(np.int64)
+        if ids.min() < 0 or ids.max() >= n:
+            raise ValueError("env ids must lie in [0, %d), got %d..%d" % (n, ids.min(), ids.max()))
+        if np.unique(ids).size != ids.size:
+            raise ValueError("env ids must be distinct")
+        return None, ids
+
     def _out_obs(self):
         return self._obs.cpu().numpy() if self.return_numpy else self._obs
 
