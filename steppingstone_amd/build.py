@@ -1,7 +1,12 @@
 """Build libsteppingstone.so (hand-written HIP for gfx950) in-tree with hipcc.
 
 hipcc cross-compiles without a GPU, so this runs in the GPU-less build container; the resulting .so travels to the
-GPU box with the repository snapshot.  `python -m steppingstone_amd.build [--force]`.
+GPU box with the repository snapshot.
+
+    python -m steppingstone_amd.build [--force] [--fuzz]      the product library (and the schedule-fuzzed test build)
+    python -m steppingstone_amd.build --variant NAME [hipcc flags ...]
+                                                              var/libss_NAME.so: the same recipe plus the given flags (-DSS_PGS_ITERS=...,
+                                                              -DSS_PROFILE_PHASES, ...), for A/B runs through STEPPINGSTONE_LIB
 """
 import os
 import subprocess
@@ -53,10 +58,11 @@ def stale(lib=LIB):
 
 
 FUZZ_LIB = os.path.join(LIBDIR, "libsteppingstone_fuzz.so")
+VARDIR = os.path.join(os.path.dirname(PKG), "var")      # git-ignored: tuning variants
 
 
 def _compile_lib(out, extra_flags, tag, verbose):
-    """Both translation units in parallel, then the link.  A compiler that does not know the optional -mllvm flag gets the plain
+    """Every translation unit in parallel, then the link.  A compiler that does not know the optional -mllvm flag gets the plain
     flags on a second pass; that pass keeps its diagnostics (a genuine compile error must be readable)."""
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
@@ -92,6 +98,13 @@ def build_fuzz(force=False, verbose=False):
     return _compile_lib(FUZZ_LIB, ["-DSS_FUZZ_SCHED"], "_fuzz", verbose)
 
 
+def build_variant(name, extra_flags, verbose=False):
+    """var/libss_<name>.so: the product recipe plus extra_flags.  A tuning build: nothing in the package loads it (point
+    STEPPINGSTONE_LIB at it: tools/ab_libs.sh, tools/state_hash.py, tools/sched_fuzz.py)."""
+    os.makedirs(VARDIR, exist_ok=True)
+    return _compile_lib(os.path.join(VARDIR, "libss_%s.so" % name), list(extra_flags), "_var_" + name, verbose)
+
+
 def build(force=False, verbose=False):
     if not force and not stale():
         return LIB
@@ -100,6 +113,10 @@ def build(force=False, verbose=False):
 
 
 if __name__ == "__main__":
+    if "--variant" in sys.argv:
+        i = sys.argv.index("--variant")
+        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], verbose=True))
+        sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     if "--fuzz" in sys.argv:
         build_fuzz(force="--force" in sys.argv, verbose=True)

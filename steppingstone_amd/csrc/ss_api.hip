@@ -85,18 +85,10 @@ static __global__ __launch_bounds__(kTempThreads) void temp_states_kernel(Params
       float sp, cp, sph, cph;
       sincosf(pitch, &sp, &cp);
       sincosf(phi, &sph, &cph);
-      float planar = dr * cp;
-      p2[0] = p1[0] + planar * cph;
-      p2[1] = p1[1] + planar * sph;
-      p2[2] = p1[2] + dr * sp;
+      place_stone(p1[0], p1[1], p1[2], dr, cp, sp, cph, sph, p2);
     }
-    float cyaw, syaw;                      // yaw only: (cos, sin) = (A, B) / |(A, B)| as in quat_roll_pitch_cs
-    {
-      const float A = 1.f - 2.f * (quat[2] * quat[2] + quat[3] * quat[3]), B = 2.f * (quat[0] * quat[3] + quat[1] * quat[2]);
-      const float n2 = A * A + B * B, inv = rsqrtf(fmaxf(n2, 1e-30f));
-      cyaw = n2 > 1e-30f ? A * inv : 1.f;
-      syaw = n2 > 1e-30f ? B * inv : 0.f;
-    }
+    float roll, pitch, cyaw, syaw;         // the yaw only: roll and pitch are dead code here
+    quat_roll_pitch_cs(quat, roll, pitch, cyaw, syaw);
     float f[5];
     target_features(pos, cyaw, syaw, p2, tilt2, f);
 #pragma unroll
@@ -145,27 +137,19 @@ static __global__ void calib_copy_kernel(const float* __restrict__ in, float* __
   if (i < n) out[i] = in[i] + 1.0f;
 }
 
-// packed [N,186] <-> structure of arrays (pack_env / unpack_env)
-static __global__ void pack_state_kernel(Params P, float* packed) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < P.n) pack_env(P, e, packed);
-}
-static __global__ void unpack_state_kernel(Params P, const float* packed) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < P.n) unpack_env(P, e, packed);
-}
-// packed row k <-> env ids[k] (ss_get_state_envs / ss_set_state_envs).  The ids live on the device and are not checked by the host:
-// an id outside [0, N) is skipped -- its row is neither read nor written (the rule of ss_render)
-static __global__ void pack_state_ids_kernel(Params P, const int32_t* ids, int m, float* packed) {
+// packed [m,186] <-> structure of arrays (pack_env / unpack_env): row k <-> env ids[k]; ids == null: row k <-> env k.  The ids live on
+// the device and are not checked by the host: an id outside [0, N) is skipped -- its row is neither read nor written (the rule of
+// ss_render)
+static __global__ void pack_state_kernel(Params P, const int32_t* ids, int m, float* packed) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= m) return;
-  const int e = ids[k];
+  const int e = ids ? ids[k] : k;
   if (e >= 0 && e < P.n) pack_env(P, e, packed, (size_t)k);
 }
-static __global__ void unpack_state_ids_kernel(Params P, const int32_t* ids, int m, const float* packed) {
+static __global__ void unpack_state_kernel(Params P, const int32_t* ids, int m, const float* packed) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= m) return;
-  const int e = ids[k];
+  const int e = ids ? ids[k] : k;
   if (e >= 0 && e < P.n) unpack_env(P, e, packed, (size_t)k);
 }
 
@@ -232,18 +216,6 @@ struct ss_env {
 
 namespace {
 
-void window_prob(float* p, int c, bool ring) {
-  int cnt = 0;
-  for (int i = 0; i < SS_GRID; ++i)
-    for (int j = 0; j < SS_GRID; ++j) {
-      int di = std::abs(i - 5), dj = std::abs(j - 5), m = di > dj ? di : dj;
-      bool in = ring ? (m == c) : (m <= c);
-      p[i * SS_GRID + j] = in ? 1.f : 0.f;
-      cnt += in;
-    }
-  for (int k = 0; k < SS_NCELL; ++k) p[k] = p[k] / (float)cnt;
-}
-
 // Host-synchronous hook update: a <= 500-byte hipMemcpy on the null stream.  When it returns the device copy is
 // current, so every step enqueued afterwards (on any stream, or replayed from a hipGraph) sees it.
 int push_knobs(ss_env* env) {
@@ -251,17 +223,31 @@ int push_knobs(ss_env* env) {
   return SS_OK;
 }
 
+// the stone sampler reads the shared grid or the per-env grids (host mirror; the caller pushes it to the device)
+void use_grid(ss_env* env, bool per_env) {
+  env->hk.prob = per_env ? env->prob_env : env->prob_shared;
+  env->hk.per_env_prob = per_env ? 1 : 0;
+}
+
 int set_window(ss_env* env, int level, bool ring) {
   if (!env) return fail(SS_ERR_INVALID, "null handle");
   if (level < 0 || level > 5) return fail(SS_ERR_INVALID, "curriculum level must be in 0..5");
   float p[SS_NCELL];
-  window_prob(p, level, ring);
+  ss::window_prob(p, level, ring);
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(hipMemcpy(env->prob_shared, p, sizeof p, hipMemcpyHostToDevice));
   env->hk.curriculum = level;
-  env->hk.prob = env->prob_shared;
-  env->hk.per_env_prob = 0;
+  use_grid(env, false);
   return push_knobs(env);
+}
+
+int zero_state(ss_env* env) {
+  const ss::Params& P = env->P;
+  const size_t np = (size_t)P.npad;
+  SS_HIP(hipMemset(P.fstate, 0, sizeof(float) * ss::NF * np));
+  SS_HIP(hipMemset(P.istate, 0, sizeof(int) * ss::NI * np));
+  SS_HIP(hipMemset(P.terrain, 0, sizeof(float) * 120 * np));
+  return SS_OK;
 }
 
 int helpers_for(const ss_env* env, int groups) {
@@ -272,6 +258,12 @@ int helpers_for(const ss_env* env, int groups) {
 }
 
 inline dim3 grid64(const ss_env* env) { return dim3(env->P.npad / ss::kWave); }
+
+// The one place that turns env->kind into the robot's model type: f(Model{}) with Model = ss::ModelWalker3D or ss::ModelMike
+template <class F>
+auto with_model(const ss_env* env, F&& f) {
+  return env->kind == SS_WALKER3D ? f(ss::ModelWalker3D{}) : f(ss::ModelMike{});
+}
 
 // A step or rollout launch: kernel_of(helpers) is the robot's kernel with that many helper wavefronts, launched with 1 + helpers
 // wavefronts per workgroup.  helpers_for() gives 0, 1 or 3; a forced SS_HELPERS of 2 or more than 3 runs the one-helper kernel.
@@ -291,22 +283,45 @@ int launch_env_kernel(ss_env* env, const ss::StepIO& io, hipStream_t st, KernelO
 
 template <bool RANDOM>
 int launch_step(ss_env* env, const ss::StepIO& io, hipStream_t st) {
-  const bool w = env->kind == SS_WALKER3D;
-  return launch_env_kernel(env, io, st, [w](int helpers) -> StepKernel {
-    if (helpers == 3) return w ? ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 3> : ss::step_kernel_helped<ss::ModelMike, RANDOM, 3>;
-    if (helpers == 1) return w ? ss::step_kernel_helped<ss::ModelWalker3D, RANDOM, 1> : ss::step_kernel_helped<ss::ModelMike, RANDOM, 1>;
-    return w ? ss::step_kernel<ss::ModelWalker3D, RANDOM> : ss::step_kernel<ss::ModelMike, RANDOM>;
+  return with_model(env, [&](auto model) {
+    using Model = decltype(model);
+    return launch_env_kernel(env, io, st, [](int helpers) -> StepKernel {
+      if (helpers == 3) return ss::step_kernel_helped<Model, RANDOM, 3>;
+      if (helpers == 1) return ss::step_kernel_helped<Model, RANDOM, 1>;
+      return ss::step_kernel<Model, RANDOM>;
+    });
   });
 }
 
 // io.nsteps control steps in one launch, actions from the benchmark Philox stream
 int launch_rollout(ss_env* env, const ss::StepIO& io, hipStream_t st) {
-  const bool w = env->kind == SS_WALKER3D;
-  return launch_env_kernel(env, io, st, [w](int helpers) -> StepKernel {
-    if (helpers == 3) return w ? ss::rollout_kernel_helped<ss::ModelWalker3D, 3> : ss::rollout_kernel_helped<ss::ModelMike, 3>;
-    if (helpers == 1) return w ? ss::rollout_kernel_helped<ss::ModelWalker3D, 1> : ss::rollout_kernel_helped<ss::ModelMike, 1>;
-    return w ? ss::rollout_kernel<ss::ModelWalker3D> : ss::rollout_kernel<ss::ModelMike>;
+  return with_model(env, [&](auto model) {
+    using Model = decltype(model);
+    return launch_env_kernel(env, io, st, [](int helpers) -> StepKernel {
+      if (helpers == 3) return ss::rollout_kernel_helped<Model, 3>;
+      if (helpers == 1) return ss::rollout_kernel_helped<Model, 1>;
+      return ss::rollout_kernel<Model>;
+    });
   });
+}
+
+// a one-lane-per-env kernel of the robot (reset, observation, masked reset): kernel_of(Model{}) is its instantiation
+template <class KernelOf, class... Args>
+int launch_per_env(ss_env* env, hipStream_t st, KernelOf&& kernel_of, Args... args) {
+  SS_HIP(hipSetDevice(env->device));
+  hipLaunchKernelGGL(with_model(env, kernel_of), grid64(env), dim3(ss::kWave), 0, st, env->P, args...);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+// pack_state_kernel / unpack_state_kernel over m packed rows (ids == null: the whole batch, row k <-> env k)
+template <class Packed>
+int launch_state_rows(ss_env* env, void (*kernel)(ss::Params, const int32_t*, int, Packed*), const int32_t* ids, int m, Packed* packed,
+                      void* stream) {
+  SS_HIP(hipSetDevice(env->device));
+  hipLaunchKernelGGL(kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, ids, m, packed);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
 }
 
 }  // namespace
@@ -355,15 +370,15 @@ int ss_create(ss_env** out, int kind, int32_t num_envs, int device, uint64_t see
   hipError_t e4 = hipMalloc(&env->prob_shared, sizeof(float) * SS_NCELL);
   hipError_t e5 = hipMalloc(&env->dk, sizeof(ss::Knobs));
   P.knobs = env->dk;
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
+  int rc = SS_OK;
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess)
+    rc = fail(SS_ERR_ALLOC, "hipMalloc failed for the environment state");
+  if (rc == SS_OK) rc = zero_state(env);
+  if (rc == SS_OK) rc = set_window(env, 0, false);
+  if (rc != SS_OK) {      // every failure after `new`: nothing of the handle survives
     ss_destroy(env);
-    return fail(SS_ERR_ALLOC, "hipMalloc failed for the environment state");
+    return rc;
   }
-  SS_HIP(hipMemset(P.fstate, 0, sizeof(float) * ss::NF * np));
-  SS_HIP(hipMemset(P.istate, 0, sizeof(int) * ss::NI * np));
-  SS_HIP(hipMemset(P.terrain, 0, sizeof(float) * 120 * np));
-  int rc = set_window(env, 0, false);
-  if (rc != SS_OK) { ss_destroy(env); return rc; }
   *out = env;
   return SS_OK;
 }
@@ -387,14 +402,7 @@ void ss_destroy(ss_env* env) {
 
 int ss_reset(ss_env* env, float* obs, void* stream) {
   if (!env) return fail(SS_ERR_INVALID, "null handle");
-  SS_HIP(hipSetDevice(env->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (env->kind == SS_WALKER3D)
-    hipLaunchKernelGGL((ss::reset_kernel<ss::ModelWalker3D>), grid64(env), dim3(ss::kWave), 0, st, env->P, obs);
-  else
-    hipLaunchKernelGGL((ss::reset_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, st, env->P, obs);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_per_env(env, (hipStream_t)stream, [](auto model) { return ss::reset_kernel<decltype(model)>; }, obs);
 }
 
 int ss_step(ss_env* env, const float* act, float* obs, float* rew, uint8_t* done, ss_info* info, void* stream) {
@@ -544,8 +552,7 @@ int ss_set_sample_prob(ss_env* env, const double* prob, int per_env) {
     float p[SS_NCELL];
     for (int k = 0; k < SS_NCELL; ++k) p[k] = (float)prob[k];
     SS_HIP(hipMemcpy(env->prob_shared, p, sizeof p, hipMemcpyHostToDevice));
-    env->hk.prob = env->prob_shared;
-    env->hk.per_env_prob = 0;
+    use_grid(env, false);
     return push_knobs(env);
   }
   const size_t np = (size_t)env->P.npad;
@@ -554,8 +561,7 @@ int ss_set_sample_prob(ss_env* env, const double* prob, int per_env) {
   for (int e = 0; e < env->P.n; ++e)
     for (int k = 0; k < SS_NCELL; ++k) t[(size_t)k * np + e] = (float)prob[(size_t)e * SS_NCELL + k];
   SS_HIP(hipMemcpy(env->prob_env, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice));
-  env->hk.prob = env->prob_env;
-  env->hk.per_env_prob = 1;
+  use_grid(env, true);
   return push_knobs(env);
 }
 
@@ -565,8 +571,6 @@ int ss_set_sample_prob_device(ss_env* env, const float* prob, int per_env, void*
   hipStream_t st = (hipStream_t)stream;
   if (!per_env) {
     hipLaunchKernelGGL(ss::copy_prob_kernel, dim3(1), dim3(128), 0, st, prob, env->prob_shared);
-    env->hk.prob = env->prob_shared;
-    env->hk.per_env_prob = 0;
   } else {
     const size_t np = (size_t)env->P.npad;
     if (!env->prob_env) {
@@ -576,9 +580,8 @@ int ss_set_sample_prob_device(ss_env* env, const float* prob, int per_env, void*
     const int total = env->P.n * SS_NCELL;
     hipLaunchKernelGGL(ss::transpose_prob_kernel, dim3((total + 255) / 256), dim3(256), 0, st, prob, env->prob_env, env->P.n,
                        env->P.npad);
-    env->hk.prob = env->prob_env;
-    env->hk.per_env_prob = 1;
   }
+  use_grid(env, per_env != 0);
   // the pointer / flag switch travels on the same stream, behind the grid it refers to
   hipLaunchKernelGGL(ss::set_knobs_kernel, dim3(1), dim3(64), 0, st, env->dk, env->hk);
   SS_HIP(hipGetLastError());
@@ -615,10 +618,8 @@ int ss_create_temp_states(ss_env* env, float* out, void* stream) {
   SS_HIP(hipSetDevice(env->device));
   if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(SS_ERR_INVALID, "out must be 16-byte aligned");
   if (!env->obs_rows) SS_HIP(hipMalloc(&env->obs_rows, sizeof(float) * SS_OBS_DIM * (size_t)env->P.npad));
-  if (env->kind == SS_WALKER3D)
-    hipLaunchKernelGGL((ss::obs_kernel<ss::ModelWalker3D>), grid64(env), dim3(ss::kWave), 0, (hipStream_t)stream, env->P, env->obs_rows);
-  else
-    hipLaunchKernelGGL((ss::obs_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, (hipStream_t)stream, env->P, env->obs_rows);
+  int rc = launch_per_env(env, (hipStream_t)stream, [](auto model) { return ss::obs_kernel<decltype(model)>; }, env->obs_rows);
+  if (rc != SS_OK) return rc;
   hipLaunchKernelGGL(ss::temp_states_kernel, dim3(env->P.n), dim3(ss::kTempThreads), 0, (hipStream_t)stream, env->P,
                      (const float*)env->obs_rows, out);      // one workgroup per env
   SS_HIP(hipGetLastError());
@@ -689,18 +690,12 @@ int ss_debug_phase_cycles(ss_env* env, unsigned long long* out16, int reset) {
 
 int ss_get_state(ss_env* env, float* packed, void* stream) {
   if (!env || !packed) return fail(SS_ERR_INVALID, "null argument");
-  SS_HIP(hipSetDevice(env->device));
-  hipLaunchKernelGGL(ss::pack_state_kernel, dim3((env->P.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, packed);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_state_rows(env, ss::pack_state_kernel, nullptr, env->P.n, packed, stream);
 }
 
 int ss_set_state(ss_env* env, const float* packed, void* stream) {
   if (!env || !packed) return fail(SS_ERR_INVALID, "null argument");
-  SS_HIP(hipSetDevice(env->device));
-  hipLaunchKernelGGL(ss::unpack_state_kernel, dim3((env->P.n + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, packed);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_state_rows(env, ss::unpack_state_kernel, nullptr, env->P.n, packed, stream);
 }
 
 int ss_reset_masked(ss_env* env, const uint8_t* mask, float* obs, int32_t obs_stride, float* terminal_obs, void* stream) {
@@ -708,16 +703,8 @@ int ss_reset_masked(ss_env* env, const uint8_t* mask, float* obs, int32_t obs_st
   if (obs_stride != SS_OBS_DIM && obs_stride != SS_OBS_DIM + 2)
     return fail(SS_ERR_INVALID, "ss_reset_masked: obs_stride must be 60 (ss_step's obs) or 62 (ss_step_packed's block)");
   if (terminal_obs && !obs) return fail(SS_ERR_INVALID, "ss_reset_masked: terminal_obs needs obs to copy the rows from");
-  SS_HIP(hipSetDevice(env->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (env->kind == SS_WALKER3D)
-    hipLaunchKernelGGL((ss::reset_masked_kernel<ss::ModelWalker3D>), grid64(env), dim3(ss::kWave), 0, st, env->P, mask, obs,
-                       (int)obs_stride, terminal_obs);
-  else
-    hipLaunchKernelGGL((ss::reset_masked_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, st, env->P, mask, obs,
-                       (int)obs_stride, terminal_obs);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_per_env(env, (hipStream_t)stream, [](auto model) { return ss::reset_masked_kernel<decltype(model)>; }, mask, obs,
+                        (int)obs_stride, terminal_obs);
 }
 
 int ss_get_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, float* packed, void* stream) {
@@ -725,10 +712,7 @@ int ss_get_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, float* pac
   if (m < 0) return fail(SS_ERR_INVALID, "ss_get_state_envs: m must be >= 0");
   if (m > 0 && (!env_ids || !packed)) return fail(SS_ERR_INVALID, "ss_get_state_envs: env_ids and packed must be device pointers");
   if (m == 0) return SS_OK;
-  SS_HIP(hipSetDevice(env->device));
-  hipLaunchKernelGGL(ss::pack_state_ids_kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, env_ids, (int)m, packed);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_state_rows(env, ss::pack_state_kernel, env_ids, m, packed, stream);
 }
 
 int ss_set_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, const float* packed, void* stream) {
@@ -736,22 +720,12 @@ int ss_set_state_envs(ss_env* env, const int32_t* env_ids, int32_t m, const floa
   if (m < 0) return fail(SS_ERR_INVALID, "ss_set_state_envs: m must be >= 0");
   if (m > 0 && (!env_ids || !packed)) return fail(SS_ERR_INVALID, "ss_set_state_envs: env_ids and packed must be device pointers");
   if (m == 0) return SS_OK;
-  SS_HIP(hipSetDevice(env->device));
-  hipLaunchKernelGGL(ss::unpack_state_ids_kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, env->P, env_ids, (int)m,
-                     packed);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_state_rows(env, ss::unpack_state_kernel, env_ids, m, packed, stream);
 }
 
 int ss_get_obs(ss_env* env, float* obs, void* stream) {
   if (!env || !obs) return fail(SS_ERR_INVALID, "null argument");
-  SS_HIP(hipSetDevice(env->device));
-  if (env->kind == SS_WALKER3D)
-    hipLaunchKernelGGL((ss::obs_kernel<ss::ModelWalker3D>), grid64(env), dim3(ss::kWave), 0, (hipStream_t)stream, env->P, obs);
-  else
-    hipLaunchKernelGGL((ss::obs_kernel<ss::ModelMike>), grid64(env), dim3(ss::kWave), 0, (hipStream_t)stream, env->P, obs);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  return launch_per_env(env, (hipStream_t)stream, [](auto model) { return ss::obs_kernel<decltype(model)>; }, obs);
 }
 
 int ss_camera_default(ss_camera* cam) {

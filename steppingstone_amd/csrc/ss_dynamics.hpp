@@ -90,15 +90,19 @@ constexpr bool warm_in_lds(int helpers) { return helpers < 3; }
 
 // the half-tree: global (right-side) joint ids, spine first
 constexpr int kHalf[NH] = {0, 1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 16};
+// the left twin of a right-side joint (a spine joint is its own)
+constexpr int left_twin(int jr) { return jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4); }
 // joints whose angle changes sign under the y-mirror (rotation about x or z)
 constexpr bool mirror_flips(int j) { return kAxis[j] != 1; }
+// factor between a joint's value in the true world and in a lane's own world (m = +1: the true world, m = -1: its y-mirror)
+__host__ __device__ constexpr float mirror_sign(int j, float m) { return mirror_flips(j) ? m : 1.f; }
 // Policy coordinates (PHYSICS.md 2, kPolicySign): actions and observations carry sigma_j x (value about the +axis).  For the limbs
 // sigma is one physical convention on both sides (the generator asserts sigma[left] = sigma[right] for y joints and -sigma[right] for
 // x / z joints: the left one is measured about the mirrored axis), and the left lane's mirrored world holds exactly "about the
 // mirrored axis" -- so BOTH lanes convert between their own world and policy coordinates with the RIGHT twin's sigma; the spine
 // (sigma = +1) changes sign in the left lane for its z / x joints only.  The same factor serves actions in and observations out.
 __host__ __device__ constexpr float action_lane_sign(int jr, float m) {
-  return jr < 3 ? (mirror_flips(jr) ? m : 1.f) : (float)kPolicySign[jr];
+  return jr < 3 ? mirror_sign(jr, m) : (float)kPolicySign[jr];
 }
 // TRUE-world value (about the +axis, as the state arrays hold it) -> policy coordinates: sigma of the joint itself
 __host__ __device__ constexpr float policy_true_sign(int jr, int side) {

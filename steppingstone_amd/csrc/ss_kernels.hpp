@@ -13,6 +13,8 @@
 //                                get_state / set_state and by create_temp_states only.
 //   prob   [121] float shared grid, or [121][Npad] per-env grids
 #pragma once
+#include <cstdlib>
+
 #include "ss_dynamics.hpp"
 #include "../../include/steppingstone.h"
 
@@ -59,6 +61,20 @@ struct Dyn {             // full-robot dynamic state, true world (reset / obs / 
   float qd[NJ];
 };
 
+// Sampling grid of a curriculum level c (ring = false: the cells within c of the centre cell, Chebyshev distance) or of a
+// specialist level (ring = true: the cells at exactly c), uniform over those cells (PHYSICS.md 8).  Host side.
+inline void window_prob(float* p, int c, bool ring) {
+  int cnt = 0;
+  for (int i = 0; i < SS_GRID; ++i)
+    for (int j = 0; j < SS_GRID; ++j) {
+      int di = std::abs(i - 5), dj = std::abs(j - 5), m = di > dj ? di : dj;
+      bool in = ring ? (m == c) : (m <= c);
+      p[i * SS_GRID + j] = in ? 1.f : 0.f;
+      cnt += in;
+    }
+  for (int k = 0; k < SS_NCELL; ++k) p[k] = p[k] / (float)cnt;
+}
+
 SSD float yaw_sample(int i) { return (-20.0f + 4.0f * (float)i) * kDeg; }
 SSD float pitch_sample(int j) { return (-30.0f + 6.0f * (float)j) * kDeg; }
 
@@ -93,6 +109,13 @@ SSD int sample_cell(const Params& P, const Knobs& K, int e, float u) {
   return pick < 0 ? last : pick;
 }
 
+// centre of a stone dr away from its predecessor at p, in the direction (phi, pitch) given by their cos / sin (PHYSICS.md 6)
+SSD void place_stone(float px, float py, float pz, float dr, float cp, float sp, float cph, float sph, float out_p[3]) {
+  float planar = dr * cp;
+  out_p[0] = px + planar * cph;
+  out_p[1] = py + planar * sph;
+  out_p[2] = pz + dr * sp;
+}
 // draw stone k from stone k-1 (terrain table), write it to the table; returns dr and the new stone's data
 SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int k, float out_p[3], float out_n[3],
                      float out_t[2], float out_h[2], bool store = true) {
@@ -116,10 +139,7 @@ SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int 
   float sp, cp, sph, cph;
   sincosf(pitch, &sp, &cp);
   sincosf(phi, &sph, &cph);
-  float planar = dr * cp;
-  out_p[0] = px + planar * cph;
-  out_p[1] = py + planar * sph;
-  out_p[2] = pz + dr * sp;
+  place_stone(px, py, pz, dr, cp, sp, cph, sph, out_p);
   out_t[0] = xt; out_t[1] = yt;
   out_h[0] = cph; out_h[1] = sph;
   stone_normal(phi, xt, yt, out_n);
@@ -135,13 +155,6 @@ SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int 
     if (prov < k + 1) P.istate[e + I_PROV * np] = k + 1;
   }
   return dr;
-}
-
-SSD void quat_rpy(const float q[4], float& roll, float& pitch, float& yaw) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  roll = atan2f(2.f * (w * x + y * z), 1.f - 2.f * (x * x + y * y));
-  pitch = asinf(fminf(fmaxf(2.f * (w * y - z * x), -1.f), 1.f));
-  yaw = atan2f(2.f * (w * z + x * y), 1.f - 2.f * (y * y + z * z));
 }
 
 SSD float planar_dist(const float a[3], const float b[3]) {
@@ -171,8 +184,15 @@ SSD void target_features(const float pos[3], float cy, float sy, const float sp[
 }
 
 SSD float clip5(float x) { return fminf(fmaxf(x, -5.f), 5.f); }
+// joint entries of the observation (PHYSICS.md 5), in POLICY coordinates (PHYSICS.md 2): ps = +-1 is the joint's kPolicySign, applied
+// to the true-world angle and to the middle of its true range (the negations are exact)
+SSD float obs_angle(float ps, float q, float mid, float span) { return clip5(2.f * (ps * q - ps * mid) / span); }
+SSD float obs_rate(float ps, float qd) { return clip5(0.1f * (ps * qd)); }
 
-// observation (PHYSICS.md section 5) written row-major to obs[60]
+// observation (PHYSICS.md section 5) written row-major to obs[60].  The base / contact / target entries (obs 0-5, 48-59) are
+// written a second time in emit_outputs, on the lane-pair layout of the step kernels (merging the two moves the instructions of the
+// benchmarked kernel); tests/test_gpu_env_control.py::test_reset_of_finished_envs_equals_auto_reset and
+// tests/test_gpu_parity.py::test_reset_matches_oracle hold the two to the same bits.
 template <class Model>
 SSD void write_obs(const Dyn& s, float z_init, int flags, const Cache& c, float* obs) {
   float roll, pitch, sy, cy;
@@ -192,9 +212,9 @@ SSD void write_obs(const Dyn& s, float z_init, int flags, const Cache& c, float*
     constexpr int j = decltype(Jc)::value;
     constexpr float mid = 0.5f * (Model::lo[j] + Model::hi[j]);
     constexpr float span = Model::hi[j] - Model::lo[j];
-    constexpr float ps = (float)kPolicySign[j];       // policy coordinates, PHYSICS.md 2 (negations are exact: same bits as emit_outputs)
-    obs[6 + j] = clip5(2.f * (ps * s.q[j] - ps * mid) / span);
-    obs[27 + j] = clip5(0.1f * (ps * s.qd[j]));
+    constexpr float ps = (float)kPolicySign[j];
+    obs[6 + j] = obs_angle(ps, s.q[j], mid, span);
+    obs[27 + j] = obs_rate(ps, s.qd[j]);
   });
   obs[48] = (flags & 1) ? 1.f : 0.f;
   obs[49] = (flags & 2) ? 1.f : 0.f;
@@ -279,17 +299,29 @@ SSD void cache_from_terrain(const Params& P, int e, int n, Cache& c, float (&hd)
   }
 }
 
-// PHYSICS.md section 7
-template <class Model>
-SSD void env_reset(const Params& P, int e, Dyn& s, Cache& c, uint32_t& ctr, float& pot, float& z_init, float& nn_dr) {
-  const size_t np = (size_t)P.npad;
-  P.istate[e + I_PROV * np] = 0;                // the whole path is provisional again: nothing is written to the terrain table
+// the provisional path of a fresh episode (PHYSICS.md 6): stones along +x, 0.75 m apart, flat
+SSD void flat_path(Stones& c) {
 #pragma unroll
   for (int sl = 0; sl < 3; ++sl) {
     c.p[sl][0] = 0.75f * (float)sl; c.p[sl][1] = 0.f; c.p[sl][2] = 0.f;
     c.nrm[sl][0] = 0.f; c.nrm[sl][1] = 0.f; c.nrm[sl][2] = 1.f;
     c.tilt[sl][0] = 0.f; c.tilt[sl][1] = 0.f;
   }
+}
+// draw of the reset joint noise for global joint gj (PHYSICS.md section 7); r = the 6 Philox blocks of the reset
+template <class Model, int GJ>
+SSD float reset_angle(const uint32_t (&r)[6][4]) {
+  constexpr float q0 = Model::q0[GJ], lo = Model::lo[GJ] + 0.02f, hi = Model::hi[GJ] - 0.02f;
+  float q = q0 + 0.05f * (2.f * u01(r[GJ / 4][GJ % 4]) - 1.f);
+  return fminf(fmaxf(q, lo), hi);
+}
+
+// PHYSICS.md section 7
+template <class Model>
+SSD void env_reset(const Params& P, int e, Dyn& s, Cache& c, uint32_t& ctr, float& pot, float& z_init, float& nn_dr) {
+  const size_t np = (size_t)P.npad;
+  P.istate[e + I_PROV * np] = 0;                // the whole path is provisional again: nothing is written to the terrain table
+  flat_path(c);
   s.pos[0] = 0.f; s.pos[1] = 0.f; s.pos[2] = Model::stand_height + 0.01f;
   s.quat[0] = 1.f; s.quat[1] = s.quat[2] = s.quat[3] = 0.f;
 #pragma unroll
@@ -299,9 +331,7 @@ SSD void env_reset(const Params& P, int e, Dyn& s, Cache& c, uint32_t& ctr, floa
   for (int b = 0; b < 6; ++b) env_block(P, e, ctr, r[b]);
   static_for<0, NJ>([&](auto Jc) {
     constexpr int j = decltype(Jc)::value;
-    constexpr float q0 = Model::q0[j], lo = Model::lo[j] + 0.02f, hi = Model::hi[j] - 0.02f;
-    float q = q0 + 0.05f * (2.f * u01(r[j / 4][j % 4]) - 1.f);
-    s.q[j] = fminf(fmaxf(q, lo), hi);
+    s.q[j] = reset_angle<Model, j>(r);
     s.qd[j] = 0.f;
   });
   z_init = s.pos[2];
@@ -339,12 +369,35 @@ struct StepIO {
                                   // (0: every step overwrites the same block)
 };
 
-// draw of the reset joint noise for global joint gj (PHYSICS.md section 7); r = the 6 Philox blocks of the reset
-template <class Model, int GJ>
-SSD float reset_angle(const uint32_t (&r)[6][4]) {
-  constexpr float q0 = Model::q0[GJ], lo = Model::lo[GJ] + 0.02f, hi = Model::hi[GJ] - 0.02f;
-  float q = q0 + 0.05f * (2.f * u01(r[GJ / 4][GJ % 4]) - 1.f);
-  return fminf(fmaxf(q, lo), hi);
+// The base state between the TRUE world and a lane's own world in LDS (m = +1: the right lane's is the true world; m = -1: the left
+// lane's is its y-mirror, which negates y, the quaternion's x / z and the angular velocity's x / z)
+SSD void put_base(const Lds& L, float m, const float pos[3], const float quat[4], const float w[3], const float v[3]) {
+  L.s(S_POS + 0) = pos[0]; L.s(S_POS + 1) = m * pos[1]; L.s(S_POS + 2) = pos[2];
+  L.s(S_QUAT + 0) = quat[0]; L.s(S_QUAT + 1) = m * quat[1]; L.s(S_QUAT + 2) = quat[2]; L.s(S_QUAT + 3) = m * quat[3];
+  L.s(S_VW + 0) = m * w[0]; L.s(S_VW + 1) = w[1]; L.s(S_VW + 2) = m * w[2];
+  L.s(S_VV + 0) = v[0]; L.s(S_VV + 1) = m * v[1]; L.s(S_VV + 2) = v[2];
+}
+SSD void get_base(const Lds& L, float m, float pos[3], float quat[4], SV& v0) {
+  pos[0] = L.s(S_POS); pos[1] = m * L.s(S_POS + 1); pos[2] = L.s(S_POS + 2);
+  quat[0] = L.s(S_QUAT); quat[1] = m * L.s(S_QUAT + 1); quat[2] = L.s(S_QUAT + 2); quat[3] = m * L.s(S_QUAT + 3);
+  v0 = SV{{m * L.s(S_VW), L.s(S_VW + 1), m * L.s(S_VW + 2)}, {L.s(S_VV), m * L.s(S_VV + 1), L.s(S_VV + 2)}};
+}
+// ... and this lane's joints (mirror_sign)
+SSD void put_joints(const Lds& L, float m, const float (&q)[NH], const float (&qd)[NH]) {
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    const float sg = mirror_sign(jr, m);
+    L.s(S_Q + k) = sg * q[k];
+    L.s(S_QD + k) = sg * qd[k];
+  });
+}
+SSD void get_joints(const Lds& L, float m, float (&q)[NH], float (&qd)[NH]) {
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    const float sg = mirror_sign(jr, m);
+    q[k] = sg * L.s(S_Q + k);
+    qd[k] = sg * L.s(S_QD + k);
+  });
 }
 
 // ---- output stage of a control step: observation / reward / done / info rows and the bulk of the state write-back ----
@@ -389,21 +442,20 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
     // per-joint state + observation entries: own limbs by each lane, spine by the right lane
     static_for<0, NH>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-      constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);
+      constexpr int jl = left_twin(jr);
       const int gj = side ? jl : jr;
       if (jr >= 3 || side == 0) {
         // The observation carries POLICY coordinates (PHYSICS.md 2): ps = kPolicySign of THIS joint (left x / z joints: about the
         // mirrored axis; knees: negative in flexion), applied to the true-world angle and to the middle of its true range (a left
-        // x / z joint's true range is (-hi, -lo) of its right twin's).  Same expression, same bits as write_obs.  The state arrays
-        // keep angles about the +axis.
+        // x / z joint's true range is (-hi, -lo) of its right twin's).  The state arrays keep angles about the +axis.
         constexpr float midr = 0.5f * (Model::lo[jr] + Model::hi[jr]);
         constexpr float span = Model::hi[jr] - Model::lo[jr];
         const float ps = policy_true_sign(jr, side);
         const float mid = (side && mirror_flips(jr)) ? -midr : midr;
         Fo[(F_Q + gj) * np] = o.qt[k];
         Fo[(F_QD + gj) * np] = o.qdt[k];
-        SS_OBS(6 + gj) = clip5(2.f * (ps * o.qt[k] - ps * mid) / span);
-        SS_OBS(27 + gj) = clip5(0.1f * (ps * o.qdt[k]));
+        SS_OBS(6 + gj) = obs_angle(ps, o.qt[k], mid, span);
+        SS_OBS(27 + gj) = obs_rate(ps, o.qdt[k]);
       }
     });
     if (side == 0) {
@@ -412,6 +464,7 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
       float vw[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) vw[i] = R[i][0] * o.v0.v[0] + R[i][1] * o.v0.v[1] + R[i][2] * o.v0.v[2];
+      // obs 0-5 and 48-59: the same entries as in write_obs (see there for the tests that pin the two copies together).
       // a reset leaves the identity orientation: roll = pitch = yaw = 0 exactly; otherwise the values of the final orientation
       const float r2 = o.do_reset ? 0.f : o.roll, p2 = o.do_reset ? 0.f : o.pitch;
       const float cy = o.do_reset ? 1.f : o.cyaw, sy = o.do_reset ? 0.f : o.syaw;
@@ -534,15 +587,8 @@ __device__ __forceinline__ void emit_from_handoff(const Params& P, const StepIO&
   const int e = valid ? e_raw : P.n - 1;
   const float m = side ? -1.f : 1.f;
   StepOut o;
-  o.pos[0] = L.s(S_POS); o.pos[1] = m * L.s(S_POS + 1); o.pos[2] = L.s(S_POS + 2);
-  o.quat[0] = L.s(S_QUAT); o.quat[1] = m * L.s(S_QUAT + 1); o.quat[2] = L.s(S_QUAT + 2); o.quat[3] = m * L.s(S_QUAT + 3);
-  o.v0 = SV{{m * L.s(S_VW), L.s(S_VW + 1), m * L.s(S_VW + 2)}, {L.s(S_VV), m * L.s(S_VV + 1), L.s(S_VV + 2)}};
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    const float sg = mirror_flips(jr) ? m : 1.f;
-    o.qt[k] = sg * L.s(S_Q + k);
-    o.qdt[k] = sg * L.s(S_QD + k);
-  });
+  get_base(L, m, o.pos, o.quat, o.v0);
+  get_joints(L, m, o.qt, o.qdt);
   o.r = L.hs(kHandOut + 0);
   o.z_init = L.hs(kHandOut + 1);
   {   // the lane pair shares the word: the right lane left the leading part of the episode return, the left lane the trailing part
@@ -575,7 +621,7 @@ SSD void random_actions_half(const Params& P, int e, int side, float m, uint32_t
   for (int b = 0; b < 6; ++b) philox4x32_10(6u * tt + b, 1u, P.env_offset + ((uint32_t)e & P.id_mask), 0u, P.seed_lo, P.seed_hi, ra[b]);
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);
+    constexpr int jl = left_twin(jr);
     const float sg = action_lane_sign(jr, m);
     const uint32_t bits = side ? ra[jl / 4][jl % 4] : ra[jr / 4][jr % 4];
     write(k, sg * (2.f * u01(bits) - 1.f));
@@ -634,7 +680,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   for (int i = 0; i < 6; ++i) gin[7 + i] = F[(F_VEL + i) * np];
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);         // the left twin of a right-side joint
+    constexpr int jl = left_twin(jr);
     const int gj = side ? jl : jr;
     qin[k] = F[(F_Q + gj) * np];
     qdin[k] = F[(F_QD + gj) * np];
@@ -643,20 +689,12 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   if constexpr (!RANDOM_ACT) {
     static_for<0, NH>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-      constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);
+      constexpr int jl = left_twin(jr);
       ain[k] = io.act[(size_t)e * NJ + (side ? jl : jr)];
     });
   }
-  L.s(S_POS + 0) = gin[0]; L.s(S_POS + 1) = m * gin[1]; L.s(S_POS + 2) = gin[2];
-  L.s(S_QUAT + 0) = gin[3]; L.s(S_QUAT + 1) = m * gin[4]; L.s(S_QUAT + 2) = gin[5]; L.s(S_QUAT + 3) = m * gin[6];
-  L.s(S_VW + 0) = m * gin[7]; L.s(S_VW + 1) = gin[8]; L.s(S_VW + 2) = m * gin[9];
-  L.s(S_VV + 0) = gin[10]; L.s(S_VV + 1) = m * gin[11]; L.s(S_VV + 2) = gin[12];
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    const float sg = mirror_flips(jr) ? m : 1.f;
-    L.s(S_Q + k) = sg * qin[k];
-    L.s(S_QD + k) = sg * qdin[k];
-  });
+  put_base(L, m, gin, gin + 3, gin + 7, gin + 10);
+  put_joints(L, m, qin, qdin);
 
   const int nsteps = ROLLOUT ? io.nsteps : 1;
 #pragma unroll 1
@@ -717,9 +755,9 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   SS_PROFE(1);       // address arithmetic + issue of the epilogue's global loads
 
   // 3-4. back to the true world; the pair shares its feet
-  float pos[3] = {L.s(S_POS), m * L.s(S_POS + 1), L.s(S_POS + 2)};
-  float quat[4] = {L.s(S_QUAT), m * L.s(S_QUAT + 1), L.s(S_QUAT + 2), m * L.s(S_QUAT + 3)};
-  SV v0 = {{m * L.s(S_VW), L.s(S_VW + 1), m * L.s(S_VW + 2)}, {L.s(S_VV), m * L.s(S_VV + 1), L.s(S_VV + 2)}};
+  float pos[3], quat[4];
+  SV v0;
+  get_base(L, m, pos, quat, v0);
   elapsed += 1;
   const float my_sole[3] = {fr.sole[0], m * fr.sole[1], fr.sole[2]};
   float ot_sole[3];
@@ -838,11 +876,9 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   if (do_reset) {
     // PHYSICS.md section 7: provisional terrain (prov_from = 0: no table writes), standing pose, joint noise from 6 Philox blocks
     if (valid && side == 0) P.istate[e + I_PROV * np] = 0;
+    flat_path(c);
 #pragma unroll
     for (int sl = 0; sl < 3; ++sl) {
-      c.p[sl][0] = 0.75f * (float)sl; c.p[sl][1] = 0.f; c.p[sl][2] = 0.f;
-      c.nrm[sl][0] = 0.f; c.nrm[sl][1] = 0.f; c.nrm[sl][2] = 1.f;
-      c.tilt[sl][0] = 0.f; c.tilt[sl][1] = 0.f;
       hd[sl][0] = 1.f; hd[sl][1] = 0.f;
       L.q2(kLdsHead + sl) = make_float2(1.f, 0.f);
     }
@@ -873,12 +909,13 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     n = 1; count = 0; elapsed = 0; flags = 0; ep_ret = 0.f; ep_lo = 0.f;
   }
   SS_PROFE(7);       // reset branch (Philox blocks)
-  // joint values of this lane in the TRUE world (after the optional reset)
+  // joint values of this lane in the TRUE world (after the optional reset).  Read per joint on purpose: get_joints() in the else
+  // branch of one `if (do_reset)` is the same values and about 2 900 moved instructions in every step / rollout kernel
   float qt[NH], qdt[NH];
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = jr < 3 ? jr : (jr < 8 ? jr + 5 : jr + 4);
-    const float sg = mirror_flips(jr) ? m : 1.f;
+    constexpr int jl = left_twin(jr);
+    const float sg = mirror_sign(jr, m);
     if (do_reset) {
       qt[k] = side ? reset_angle<Model, jl>(rr) : reset_angle<Model, jr>(rr);
       qdt[k] = 0.f;
@@ -893,16 +930,8 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   if constexpr (ROLLOUT) {
     // the LDS copy of the state is what comes next (the next step, a helper's output stage): refresh what the env logic changed
     if (do_reset) {
-      L.s(S_POS + 0) = pos[0]; L.s(S_POS + 1) = m * pos[1]; L.s(S_POS + 2) = pos[2];
-      L.s(S_QUAT + 0) = quat[0]; L.s(S_QUAT + 1) = m * quat[1]; L.s(S_QUAT + 2) = quat[2]; L.s(S_QUAT + 3) = m * quat[3];
-      L.s(S_VW + 0) = m * v0.w[0]; L.s(S_VW + 1) = v0.w[1]; L.s(S_VW + 2) = m * v0.w[2];
-      L.s(S_VV + 0) = v0.v[0]; L.s(S_VV + 1) = m * v0.v[1]; L.s(S_VV + 2) = v0.v[2];
-      static_for<0, NH>([&](auto Kc) {
-        constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-        const float sg = mirror_flips(jr) ? m : 1.f;
-        L.s(S_Q + k) = sg * qt[k];
-        L.s(S_QD + k) = sg * qdt[k];
-      });
+      put_base(L, m, pos, quat, v0.w, v0.v);
+      put_joints(L, m, qt, qdt);
     }
     if (advanced || do_reset) {
 #pragma unroll

@@ -50,19 +50,6 @@ float ss_host_xchg(float x) {
 }
 void ss_host_wave_sync() { t_wave->wait(); }
 
-namespace {
-void window_prob(float* p, int c) {
-  int cnt = 0;
-  for (int i = 0; i < 11; ++i)
-    for (int j = 0; j < 11; ++j) {
-      int di = std::abs(i - 5), dj = std::abs(j - 5), m = di > dj ? di : dj;
-      p[i * 11 + j] = (m <= c) ? 1.f : 0.f;
-      cnt += (m <= c);
-    }
-  for (int k = 0; k < 121; ++k) p[k] /= (float)cnt;
-}
-}  // namespace
-
 extern "C" {
 
 // one control step of n envs: packed state in/out [n,186], act [n,21]; outputs obs [n,60], rew, done, info
@@ -75,7 +62,7 @@ int hh_step(int kind, int n, unsigned long long seed, int curriculum, const doub
   P.npad = (n + 63) / 64 * 64;
   std::vector<float> f((size_t)ss::NF * P.npad, 0.f), terr((size_t)120 * P.npad, 0.f), pr(121);
   std::vector<int> is((size_t)ss::NI * P.npad, 0);
-  window_prob(pr.data(), curriculum);
+  ss::window_prob(pr.data(), curriculum, false);
   if (prob) for (int k = 0; k < 121; ++k) pr[k] = (float)prob[k];
   ss::Knobs K;
   K.prob = pr.data(); K.per_env_prob = 0; K.curriculum = curriculum; K.power = 1.f; K.auto_reset = 1;

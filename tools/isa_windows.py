@@ -13,7 +13,11 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-signed-zeros", "-ffp-contract=on"]   # as build.py compiles ss_rollout3.hip
+sys.path.insert(0, ROOT)
+from steppingstone_amd.build import FLAGS, NO_MAX_ILP, OPTIONAL_FLAGS, hipcc  # noqa: E402
+
+# the kernel lives in ss_rollout3.hip: compiled as build.py compiles that unit
+FLAGS = FLAGS + ([] if "ss_rollout3.hip" in NO_MAX_ILP else OPTIONAL_FLAGS)
 KERNEL = "_ZN2ss21rollout_kernel_helpedINS_13ModelWalker3DELi3EEEvNS_6ParamsENS_6StepIOE"
 
 
@@ -44,7 +48,7 @@ def main():
         src, out = os.path.join(d, "one.hip"), os.path.join(d, "one.s")
         open(src, "w").write('#include <hip/hip_runtime.h>\n#include "%s"\ntemplate __global__ void ss::rollout_kernel_helped<ss::ModelWalker3D, 3>'
                              '(ss::Params, ss::StepIO);\n' % os.path.join(ROOT, "steppingstone_amd", "csrc", "ss_kernels.hpp"))
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + sys.argv[1:] + ["-S", "--cuda-device-only", src, "-o", out],
+        subprocess.check_call([hipcc()] + FLAGS + sys.argv[1:] + ["-S", "--cuda-device-only", src, "-o", out],
                               stderr=subprocess.DEVNULL)
         text = open(out).read().split("\n")
     a = next(i for i, l in enumerate(text) if l.startswith(KERNEL + ":"))

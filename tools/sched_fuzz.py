@@ -12,7 +12,8 @@
 Configurations: both robots x {three helpers, one helper, plain kernel} x {one launch per step with an action tensor (steps/launch=0 below), one launch per step with
 on-device actions, 32 steps per launch}, curriculum 5
 (stone draws, resets, target advances all occur), plus ragged tiny batches (1 ... 700 envs).  Two runs that print the same lines
-computed the same bits on every env-step.  tools/sched_fuzz.sh runs plain once and fuzzed three times and diffs."""
+computed the same bits on every env-step.  `python -m steppingstone_amd.build --fuzz` builds lib/libsteppingstone_fuzz.so; run this once
+plain and a few times with STEPPINGSTONE_LIB pointing at it, and diff the lines (tests/test_gpu_sched_fuzz.py does)."""
 import os
 import sys
 
