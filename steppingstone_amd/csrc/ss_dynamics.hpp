@@ -52,8 +52,10 @@ constexpr int kLdsHead = 36;           // 3 float2: (cos, sin) of the heading of
                                        // region A's 40 are beyond the operators (0..35) and beyond the output staging (the first 2240 floats)
 constexpr int kScalarBase = kSlotsA * kWave * 4;   // region B, in floats
 // helper-wavefront variant (small batches): a hand-off region behind the main wavefront's 40 slots -- the joint records
-// of the spine+leg chain (8 x 9 floats), the base Cholesky factor (21), and back: the six Lambda_own columns (36)
-constexpr int kHandJc = 0, kHandL0 = 72, kHandLc = 93, kHandDet = 129, kHandAct = 146, kHandFloats = 158, kHandCs = kHandLc;   // Det: Rf 9, pen 4 (single-helper variant only), flags (active | cslot << 4 | contact << 12 | on_target << 13), sole 3; Act: the next step's 12 actions (rollout kernel); Cs: cos[12], sin[12] of the joint angles, aliasing Lc (dead between barriers #0 and #2)
+// of the spine+leg chain (8 x kRecWords floats), the base Cholesky factor (kCholWords), and back: the six Lambda_own columns (36)
+constexpr int kRecWords = 9;           // a joint record in the hand-off region: cs, sn, Dinv, Uw[3], Uv[3] (put_rec / get_rec)
+constexpr int kCholWords = 15 + 6;     // the base factor there: l[15], di[6] (put_chol / get_chol)
+constexpr int kHandJc = 0, kHandL0 = kHandJc + 8 * kRecWords, kHandLc = kHandL0 + kCholWords, kHandDet = 129, kHandAct = 146, kHandFloats = 158, kHandCs = kHandLc;   // Det: Rf 9, pen 4 (single-helper variant only), flags (active | cslot << 4 | contact << 12 | on_target << 13), sole 3; Act: the next step's 12 actions (rollout kernel); Cs: cos[12], sin[12] of the joint angles, aliasing Lc (dead between barriers #0 and #2)
 // The directions of the 12 contact rows (36 floats) and the 4 Baumgarte terms, computed by helper 0: they take the place of the
 // leg joint records once every helper has loaded those (written after barrier #2, read by the main wavefront after #3).
 // The velocity-product bias forces of the massive spine bodies (3, 2, 1) and of the base, computed by helper 1 between barriers
@@ -61,8 +63,8 @@ constexpr int kHandJc = 0, kHandL0 = 72, kHandLc = 93, kHandDet = 129, kHandAct 
 // at the end of the #1 -> #2 window (after it has read the biases).
 constexpr bool bias_offload(int helpers) { return helpers >= 3; }
 constexpr int kHandBias = kHandJc;
-static_assert(24 <= 3 * 9, "biases fit the spine records' place");
-constexpr int kHandRows = kHandJc + 3 * 9;
+static_assert(24 <= 3 * kRecWords, "biases fit the spine records' place");
+constexpr int kHandRows = kHandJc + 3 * kRecWords;
 // Three-helper variants (at most 8192 envs: one workgroup per CU): the rows get a place of their own behind the region, so that
 // helper 0 can write them BEFORE barrier #2 (as soon as it has them, round 6) and the main wavefront can fetch them and form their
 // moment parts while it waits at barrier #3 for the operators instead of after it.
@@ -75,7 +77,7 @@ constexpr bool rows_offload(int helpers) { return helpers >= 3; }
 constexpr int kHandSlots = (kHandFloats + 3) / 4;  // float4-slots per lane
 // (a larger hand-off region is not free: 81 KiB per workgroup cost 6 us per launch, 99 KiB 14 us -- measured)
 static_assert(kLdsSlots + kHandSlots <= 80, "two helper-variant workgroups must fit the 160 KiB of a CU (16384 envs: 512 workgroups)");
-static_assert(kHandRows + 40 <= kHandJc + 8 * 9, "rows fit the leg records' place");
+static_assert(kHandRows + 40 <= kHandJc + 8 * kRecWords, "rows fit the leg records' place");
 constexpr int kHandBase = kLdsSlots * kWave * 4;   // in floats
 constexpr int NH = 12;                 // joints per half
 enum { S_ACT = 0, S_Q = 12, S_QD = 24, S_WLAM = 36, S_POS = 48, S_QUAT = 51, S_VW = 55, S_VV = 58, S_STP = 61, S_STN = 70,
@@ -201,14 +203,41 @@ SSD void warm_clear(Warm& w) {
   w.key = 0;
 }
 
-struct JRec {      // what the ABA leaves behind per joint
-  float cs, sn, Uw[3], Uv[3], Dinv, u;
+template <class T>
+struct JRecT {     // what the ABA leaves behind per joint (T = ssf2: per {leg, arm} pair of joints)
+  T cs, sn, Uw[3], Uv[3], Dinv, u;
 };
+using JRec = JRecT<float>;
+using JRec2 = JRecT<ssf2>;
+static_assert(sizeof(JRec2) == 2 * sizeof(JRec), "a pair record is two scalar records, nothing else");
 struct JointCache {
   JRec r[NH];      // indexed by position in kHalf
   Chol6 L0;
 };
 constexpr int half_pos(int j) { return j <= 7 ? j : j - 5; }   // 13..16 -> 8..11
+// the hand-off region's layout of joint record k (u stays with the main wavefront) and of the base factor: one writer, one reader
+SSD void put_rec(const Lds& L, int k, const JRec& r) {
+  L.hs(kHandJc + k * kRecWords + 0) = r.cs; L.hs(kHandJc + k * kRecWords + 1) = r.sn; L.hs(kHandJc + k * kRecWords + 2) = r.Dinv;
+#pragma unroll
+  for (int m = 0; m < 3; ++m) { L.hs(kHandJc + k * kRecWords + 3 + m) = r.Uw[m]; L.hs(kHandJc + k * kRecWords + 6 + m) = r.Uv[m]; }
+}
+SSD void get_rec(const Lds& L, int k, JRec& r) {
+  r.cs = L.hs(kHandJc + k * kRecWords + 0); r.sn = L.hs(kHandJc + k * kRecWords + 1); r.Dinv = L.hs(kHandJc + k * kRecWords + 2);
+#pragma unroll
+  for (int m = 0; m < 3; ++m) { r.Uw[m] = L.hs(kHandJc + k * kRecWords + 3 + m); r.Uv[m] = L.hs(kHandJc + k * kRecWords + 6 + m); }
+}
+SSD void put_chol(const Lds& L, const Chol6& c) {
+#pragma unroll
+  for (int m = 0; m < 15; ++m) L.hs(kHandL0 + m) = c.l[m];
+#pragma unroll
+  for (int m = 0; m < 6; ++m) L.hs(kHandL0 + 15 + m) = c.di[m];
+}
+SSD void get_chol(const Lds& L, Chol6& c) {
+#pragma unroll
+  for (int i = 0; i < 15; ++i) c.l[i] = L.hs(kHandL0 + i);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) c.di[i] = L.hs(kHandL0 + 15 + i);
+}
 
 // ---- lane-pair exchange.  Partner data lives in the mirrored world: reflect on receipt.
 // On the device this is a DPP quad_perm [1,0,3,2] move (full VALU rate, no LDS round trip like ds_bpermute).
@@ -399,32 +428,6 @@ SSD SV2 imp_down_pair_loaded(const JointCache& jc, const ssf2* ul2, const SV2& p
   d.w[ax] += ul2[k] * di;
   return d;
 }
-SSD SV2 chol6_solve_neg_pair(const Chol6& L, const SV2& b) {
-  ssf2 y[6] = {-b.w[0], -b.w[1], -b.w[2], -b.v[0], -b.v[1], -b.v[2]};
-  static_for<0, 6>([&](auto Ic) {
-    constexpr int i = decltype(Ic)::value;
-    ssf2 s = y[i];
-    static_for<0, i>([&](auto Kc) {
-      constexpr int k = decltype(Kc)::value;
-      s -= y[k] * L.template get<i, k>();
-    });
-    y[i] = s * L.di[i];
-  });
-  static_rfor<5, 0>([&](auto Ic) {
-    constexpr int i = decltype(Ic)::value;
-    ssf2 s = y[i];
-    static_for<i + 1, 6>([&](auto Kc) {
-      constexpr int k = decltype(Kc)::value;
-      s -= y[k] * L.template get<k, i>();
-    });
-    y[i] = s * L.di[i];
-  });
-  SV2 x;
-  x.w[0] = y[0]; x.w[1] = y[1]; x.w[2] = y[2]; x.v[0] = y[3]; x.v[1] = y[4]; x.v[2] = y[5];
-  return x;
-}
-
-
 // Contact-space operators for the column pair (2c, 2c+1): T = K = P_7 ... P_3 (own-foot twist per unit pelvis twist through
 // the unloaded leg; LDS), and by unit impulses on the own foot through the whole tree G (pelvis twist; LDS) and
 // Lambda_own (own-foot twist; returned as columns of three pairs).  Two columns share every instruction (packed f32).
@@ -492,7 +495,7 @@ template <class Model, int CPAIR>
 SSD LamPair operator_pair_b(const Lds& L, const JointCache& jc, OpCarry& oc) {
   SV2 p = oc.p;
   static_rfor<2, 0>([&](auto Jc) { p = imp_up_pair<Model, decltype(Jc)::value>(jc, oc.ul2, p); });
-  SV2 d = chol6_solve_neg_pair(jc.L0, p);
+  SV2 d = chol6_solve_neg(jc.L0, p);
   static_for<0, 3>([&](auto Jc) { d = imp_down_pair_loaded<Model, decltype(Jc)::value>(jc, oc.ul2, d); });
   {
     // partner's columns 2c, 2c+1 in this lane's world (y-mirror: axial part (-,+,-), polar part (+,-,+))
@@ -672,6 +675,21 @@ SSD void jacobian_rows(const DetectOut& det, const Lds& L, ssf2 (&rWp)[12][3], f
   });
 }
 
+// Pass 3 of the ABA through joint JT (one scalar joint, or a {leg, arm} pair): the child body's acceleration from the parent's
+// (aprev; twist vb, joint rate qd), the joint acceleration in qdd
+template <class JT, class T>
+SSD SVT<T> aba_acc(const JRecT<T>& r, const T& qd, const SVT<T>& aprev, const SVT<T>& vb, T& qdd) {
+  constexpr int ax = JT::AX, ai = (ax + 1) % 3, aj = (ax + 2) % 3;
+  SVT<T> a = xmotion<JT>(r.cs, r.sn, aprev);
+  a.w[ai] += qd * vb.w[aj]; a.w[aj] -= qd * vb.w[ai];
+  a.v[ai] += qd * vb.v[aj]; a.v[aj] -= qd * vb.v[ai];
+  T dotv = r.Uw[0] * a.w[0] + r.Uw[1] * a.w[1] + r.Uw[2] * a.w[2] + r.Uv[0] * a.v[0] + r.Uv[1] * a.v[1] +
+           r.Uv[2] * a.v[2];
+  qdd = r.Dinv * (r.u - dotv);
+  a.w[ax] += qdd;
+  return a;
+}
+
 #ifndef SS_HOST_HARNESS
 // Helper wavefronts of the small-batch variant (one workgroup = main wavefront + HELPERS helpers, five barriers per substep):
 //   #0 state of the substep is in LDS         helpers: cos / sin of the joint angles -> LDS (main: joint torques)
@@ -787,13 +805,8 @@ __device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&&
     }
   }
   JointCache jin, jc;
-  static_for<3, 8>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value;
-    JRec& r = jin.r[k];
-    r.cs = L.hs(kHandJc + k * 9 + 0); r.sn = L.hs(kHandJc + k * 9 + 1); r.Dinv = L.hs(kHandJc + k * 9 + 2);
 #pragma unroll
-    for (int m = 0; m < 3; ++m) { r.Uw[m] = L.hs(kHandJc + k * 9 + 3 + m); r.Uv[m] = L.hs(kHandJc + k * 9 + 6 + m); }
-  });
+  for (int k = 3; k < 8; ++k) get_rec(L, k, jin.r[k]);
   OpCarry oc[HELPERS == 1 ? 3 : 1];
   static_for<0, 3>([&](auto Cc) {
     constexpr int c = decltype(Cc)::value;
@@ -801,17 +814,9 @@ __device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&&
   });
   __syncthreads();                                   // #2: spine records and the base factor
   SS_FUZZ(0x40u + helper);
-  static_for<0, 3>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value;
-    JRec& r = jin.r[k];
-    r.cs = L.hs(kHandJc + k * 9 + 0); r.sn = L.hs(kHandJc + k * 9 + 1); r.Dinv = L.hs(kHandJc + k * 9 + 2);
 #pragma unroll
-    for (int m = 0; m < 3; ++m) { r.Uw[m] = L.hs(kHandJc + k * 9 + 3 + m); r.Uv[m] = L.hs(kHandJc + k * 9 + 6 + m); }
-  });
-#pragma unroll
-  for (int i = 0; i < 15; ++i) jin.L0.l[i] = L.hs(kHandL0 + i);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) jin.L0.di[i] = L.hs(kHandL0 + 15 + i);
+  for (int k = 0; k < 3; ++k) get_rec(L, k, jin.r[k]);
+  get_chol(L, jin.L0);
   operator_records_spine(jin, jc);
   static_for<0, 3>([&](auto Cc) {
     constexpr int c = decltype(Cc)::value;
@@ -917,7 +922,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       SV2 pp = sv_pack(prev, v0);
       static_for<0, 4>([&](auto Ic) {
         constexpr int i = decltype(Ic)::value;
-        SV2 v = xmotionP<Model, 3 + i, 13 + i>(c2[i], s2[i], pp);
+        SV2 v = xmotion<PairJoint<Model, 3 + i, 13 + i>>(c2[i], s2[i], pp);
         v.w[kAxis[3 + i]] += qd2[i];
         vp[i] = v;
         pp = v;
@@ -969,8 +974,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       Ip = xinertia<Model, j>(r.cs, r.sn, I);
       pp = xforce<Model, j>(r.cs, r.sn, pa);
     };
-    struct JRec2 { ssf2 Uw[3], Uv[3], Dinv, u; };
-    JRec2 jr2[4];
+    JRec2 jr2[4];             // joints (3,13) (4,14) (5,15) (6,16)
     auto joint_pair = [&](auto Ic, ABIP I, const SV2& pA, ABIP& Ip, SV2& pp) {
       constexpr int i = decltype(Ic)::value, jl = 3 + i, ja = 13 + i, kl = 3 + i, ka = 8 + i, ax = kAxis[jl];
       constexpr int ai = (ax + 1) % 3, aj = (ax + 2) % 3;
@@ -980,6 +984,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       const ssf2 qd = qd2[i];
       const SV2& vb = vp[i];
       JRec2& r = jr2[i];
+      r.cs = c2[i]; r.sn = s2[i];     // for pass 3; passes 1 and 2 read c2 / s2 (reading them from here moves ss_api.hip's code)
       r.Uw[0] = I.A.template get<0, ax>(); r.Uw[1] = I.A.template get<1, ax>(); r.Uw[2] = I.A.template get<2, ax>();
       r.Uv[0] = I.B[ax][0]; r.Uv[1] = I.B[ax][1]; r.Uv[2] = I.B[ax][2];
       const ssf2 D = r.Uw[ax] + pkv(Daddl, Dadda);
@@ -1011,8 +1016,8 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
           pa.v[rr] = pA.v[rr] + I.B[ai][rr] * cwi + I.B[aj][rr] * cwj + Cf[rr][ai] * cvi + Cf[rr][aj] * cvj + Uv[rr] * du;
         }
       }
-      Ip = xinertiaP<Model, jl, ja>(c2[i], s2[i], I);
-      pp = xforceP<Model, jl, ja>(c2[i], s2[i], pa);
+      Ip = xinertia<PairJoint<Model, jl, ja>>(c2[i], s2[i], I);
+      pp = xforce<PairJoint<Model, jl, ja>>(c2[i], s2[i], pa);
       // scalar joint records for the contact stage (sub-register views of the pairs)
       JRec& rl = jc.r[kl];
       JRec& ra = jc.r[ka];
@@ -1053,13 +1058,8 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       });
 #if defined(__HIP_DEVICE_COMPILE__)
       if constexpr (HELPERS > 0) {     // leg joint records to the helper wavefront(s): operators, part A
-        static_for<3, 8>([&](auto Kc) {
-          constexpr int k = decltype(Kc)::value;
-          const JRec& r = jc.r[k];
-          L.hs(kHandJc + k * 9 + 0) = r.cs; L.hs(kHandJc + k * 9 + 1) = r.sn; L.hs(kHandJc + k * 9 + 2) = r.Dinv;
 #pragma unroll
-          for (int m = 0; m < 3; ++m) { L.hs(kHandJc + k * 9 + 3 + m) = r.Uw[m]; L.hs(kHandJc + k * 9 + 6 + m) = r.Uv[m]; }
-        });
+        for (int k = 3; k < 8; ++k) put_rec(L, k, jc.r[k]);
         // the machine scheduler would otherwise pull the spine and the base solve in front of the barrier (it orders memory
         // operations only), and the helpers' part A would overlap nothing
         __builtin_amdgcn_sched_barrier(0);
@@ -1137,17 +1137,9 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
     SS_PROF(4);
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (HELPERS > 0) {       // spine joint records and the base factor: operators, part B
-      static_for<0, 3>([&](auto Kc) {
-        constexpr int k = decltype(Kc)::value;
-        const JRec& r = jc.r[k];
-        L.hs(kHandJc + k * 9 + 0) = r.cs; L.hs(kHandJc + k * 9 + 1) = r.sn; L.hs(kHandJc + k * 9 + 2) = r.Dinv;
 #pragma unroll
-        for (int m = 0; m < 3; ++m) { L.hs(kHandJc + k * 9 + 3 + m) = r.Uw[m]; L.hs(kHandJc + k * 9 + 6 + m) = r.Uv[m]; }
-      });
-#pragma unroll
-      for (int m = 0; m < 15; ++m) L.hs(kHandL0 + m) = jc.L0.l[m];
-#pragma unroll
-      for (int m = 0; m < 6; ++m) L.hs(kHandL0 + 15 + m) = jc.L0.di[m];
+      for (int k = 0; k < 3; ++k) put_rec(L, k, jc.r[k]);
+      put_chol(L, jc.L0);
       __builtin_amdgcn_sched_barrier(0);
       SS_PROF(4);
       __syncthreads();                 // #2
@@ -1159,17 +1151,10 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
     // ---- pass 3: accelerations -> free velocities
     {
       auto acc_scalar = [&](auto Jc, const SV& aprev, const SV& vb) {
-        constexpr int j = decltype(Jc)::value, k = half_pos(j), ax = kAxis[j];
-        constexpr int ai = (ax + 1) % 3, aj = (ax + 2) % 3;
-        const JRec& r = jc.r[k];
-        SV a = xmotion<Model, j>(r.cs, r.sn, aprev);
-        float qd = qd_all[k];
-        a.w[ai] += qd * vb.w[aj]; a.w[aj] -= qd * vb.w[ai];
-        a.v[ai] += qd * vb.v[aj]; a.v[aj] -= qd * vb.v[ai];
-        float dotv = r.Uw[0] * a.w[0] + r.Uw[1] * a.w[1] + r.Uw[2] * a.w[2] + r.Uv[0] * a.v[0] + r.Uv[1] * a.v[1] +
-                     r.Uv[2] * a.v[2];
-        float qdd = r.Dinv * (r.u - dotv);
-        a.w[ax] += qdd;
+        constexpr int j = decltype(Jc)::value, k = half_pos(j);
+        const float qd = qd_all[k];
+        float qdd;
+        const SV a = aba_acc<Joint<Model, j>>(jc.r[k], qd, aprev, vb, qdd);
         SS_QDF(k) = qd + h * qdd;
         return a;
       };
@@ -1177,22 +1162,13 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       static_for<0, 3>([&](auto Jc) { prev = acc_scalar(Jc, prev, vs[decltype(Jc)::value]); });
       SV2 pp = sv_pack(prev, a0);
       static_for<0, 4>([&](auto Ic) {
-        constexpr int i = decltype(Ic)::value, jl = 3 + i, ja = 13 + i, ax = kAxis[jl];
-        constexpr int ai = (ax + 1) % 3, aj = (ax + 2) % 3;
-        const JRec2& r = jr2[i];
-        const SV2& vb = vp[i];
-        SV2 a = xmotionP<Model, jl, ja>(c2[i], s2[i], pp);
+        constexpr int i = decltype(Ic)::value;
         const ssf2 qd = qd2[i];
-        a.w[ai] += qd * vb.w[aj]; a.w[aj] -= qd * vb.w[ai];
-        a.v[ai] += qd * vb.v[aj]; a.v[aj] -= qd * vb.v[ai];
-        ssf2 dotv = r.Uw[0] * a.w[0] + r.Uw[1] * a.w[1] + r.Uw[2] * a.w[2] + r.Uv[0] * a.v[0] + r.Uv[1] * a.v[1] +
-                    r.Uv[2] * a.v[2];
-        ssf2 qdd = r.Dinv * (r.u - dotv);
-        a.w[ax] += qdd;
+        ssf2 qdd;
+        pp = aba_acc<PairJoint<Model, 3 + i, 13 + i>>(jr2[i], qd, pp, vp[i], qdd);
         const ssf2 qf = qd + qdd * h;
         SS_QDF(3 + i) = qf.x;
         SS_QDF(8 + i) = qf.y;
-        pp = a;
       });
       acc_scalar(std::integral_constant<int, 7>{}, sv_half(pp, 0), vfoot);
     }

@@ -82,22 +82,28 @@ constexpr bool on_leg_path(int b) {  // bodies whose joints lie between a foot a
   return (b >= 1 && b <= 13);
 }
 
-struct SV {  // spatial motion or force vector
-  float w[3];
-  float v[3];
+// Every type and transform below is written once over the element type T: float for one chain per lane, ssf2 for two chains that
+// share each instruction (ss_pair.hpp: the {leg, arm} pair; ss_dynamics.hpp: two columns of a contact operator).
+typedef float ssf2 __attribute__((ext_vector_type(2)));
+
+template <class T>
+struct SVT {  // spatial motion or force vector
+  T w[3];
+  T v[3];
 };
 
-struct Sym3 {  // symmetric 3x3: xx yy zz xy xz yz
-  float m[6];
+template <class T>
+struct Sym3T {  // symmetric 3x3: xx yy zz xy xz yz
+  T m[6];
   template <int I, int J>
-  SSD float& at() {
+  SSD T& at() {
     if constexpr (I == J) return m[I];
     else if constexpr (I + J == 1) return m[3];
     else if constexpr (I + J == 2) return m[4];
     else return m[5];
   }
   template <int I, int J>
-  SSD float get() const {
+  SSD T get() const {
     if constexpr (I == J) return m[I];
     else if constexpr (I + J == 1) return m[3];
     else if constexpr (I + J == 2) return m[4];
@@ -106,39 +112,51 @@ struct Sym3 {  // symmetric 3x3: xx yy zz xy xz yz
 };
 
 // articulated-body inertia [[A, B], [B^T, C]] : n = A w + B v, f = B^T w + C v
-struct ABI {
-  Sym3 A;
-  float B[3][3];
-  Sym3 C;
+template <class T>
+struct ABIT {
+  Sym3T<T> A;
+  T B[3][3];
+  Sym3T<T> C;
 };
 
-SSD void cross(const float a[3], const float b[3], float o[3]) {
-  float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
+using SV = SVT<float>;
+using Sym3 = Sym3T<float>;
+using ABI = ABIT<float>;
+using SV2 = SVT<ssf2>;
+using Sym3P = Sym3T<ssf2>;
+using ABIP = ABIT<ssf2>;
+static_assert(sizeof(SV2) == 2 * sizeof(SV) && sizeof(Sym3P) == 2 * sizeof(Sym3) && sizeof(ABIP) == 2 * sizeof(ABI),
+              "a pair type is two of the scalar type, nothing else");
+
+template <class T>
+SSD void cross(const T a[3], const T b[3], T o[3]) {
+  T x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
   o[0] = x; o[1] = y; o[2] = z;
 }
 SSD float dot3(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 SSD float dot6(const SV& a, const SV& b) { return dot3(a.w, b.w) + dot3(a.v, b.v); }
 
 // active rotation about coordinate axis AX by the angle with cosine c / sine s:  o = R v
-template <int AX>
-SSD void rot(float c, float s, const float v[3], float o[3]) {
+template <int AX, class T>
+SSD void rot(T c, T s, const T v[3], T o[3]) {
   constexpr int i = (AX + 1) % 3, j = (AX + 2) % 3;
-  float vi = v[i], vj = v[j];
+  T vi = v[i], vj = v[j];
   o[AX] = v[AX];
   o[i] = c * vi - s * vj;
   o[j] = s * vi + c * vj;
 }
 // o = R^T v
-template <int AX>
-SSD void rotT(float c, float s, const float v[3], float o[3]) {
+template <int AX, class T>
+SSD void rotT(T c, T s, const T v[3], T o[3]) {
   constexpr int i = (AX + 1) % 3, j = (AX + 2) % 3;
-  float vi = v[i], vj = v[j];
+  T vi = v[i], vj = v[j];
   o[AX] = v[AX];
   o[i] = c * vi + s * vj;
   o[j] = c * vj - s * vi;
 }
 
 // o = r x f with constexpr r = Model::r[J]
+// (not merged with cross_rP of ss_pair.hpp: that one adds rx and ry to o2 in the other order, which rounds differently)
 template <class Model, int J>
 SSD void cross_r(const float f[3], float o[3]) {
   constexpr float rx = Model::r[J][0], ry = Model::r[J][1], rz = Model::r[J][2];
@@ -152,100 +170,109 @@ template <class Model, int J>
 constexpr bool has_offset() {
   return Model::r[J][0] != 0.f || Model::r[J][1] != 0.f || Model::r[J][2] != 0.f;
 }
-
-// motion vector parent frame -> child frame of joint J:  w_c = R^T w_p,  v_c = R^T (v_p + w_p x r)
+// What a transform through a joint takes from the model at compile time: the rotation axis AX, whether the link offset r is non-zero,
+// and o = r x f.  This one is the scalar joint J; PairJoint (ss_pair.hpp) is the {leg, arm} pair of joints.
 template <class Model, int J>
-SSD SV xmotion(float c, float s, const SV& p) {
-  constexpr int AX = kAxis[J];
-  SV o;
+struct Joint {
+  static constexpr int AX = kAxis[J];
+  static constexpr bool offset = has_offset<Model, J>();
+  static SSD void cross_r(const float f[3], float o[3]) { ss::cross_r<Model, J>(f, o); }
+};
+
+// motion vector parent frame -> child frame through joint JT:  w_c = R^T w_p,  v_c = R^T (v_p + w_p x r)
+template <class JT, class T>
+SSD SVT<T> xmotion(T c, T s, const SVT<T>& p) {
+  constexpr int AX = JT::AX;
+  SVT<T> o;
   rotT<AX>(c, s, p.w, o.w);
-  float t[3] = {p.v[0], p.v[1], p.v[2]};
-  if constexpr (has_offset<Model, J>()) {
-    float rxw[3];
-    cross_r<Model, J>(p.w, rxw);  // r x w = -(w x r)
+  T t[3] = {p.v[0], p.v[1], p.v[2]};
+  if constexpr (JT::offset) {
+    T rxw[3];
+    JT::cross_r(p.w, rxw);  // r x w = -(w x r)
     t[0] -= rxw[0]; t[1] -= rxw[1]; t[2] -= rxw[2];
   }
   rotT<AX>(c, s, t, o.v);
   return o;
 }
 // force vector child frame -> parent frame:  f_p = R f_c,  n_p = R n_c + r x f_p
-template <class Model, int J>
-SSD SV xforce(float c, float s, const SV& f) {
-  constexpr int AX = kAxis[J];
-  SV o;
+template <class JT, class T>
+SSD SVT<T> xforce(T c, T s, const SVT<T>& f) {
+  constexpr int AX = JT::AX;
+  SVT<T> o;
   rot<AX>(c, s, f.v, o.v);
   rot<AX>(c, s, f.w, o.w);
-  if constexpr (has_offset<Model, J>()) {
-    float t[3];
-    cross_r<Model, J>(o.v, t);
+  if constexpr (JT::offset) {
+    T t[3];
+    JT::cross_r(o.v, t);
     o.w[0] += t[0]; o.w[1] += t[1]; o.w[2] += t[2];
   }
   return o;
 }
 
 // S' = R S R^T for a symmetric block, rotation in the (i,j) plane
-template <int AX>
-SSD Sym3 rot_sym(float c, float s, const Sym3& S) {
+template <int AX, class T>
+SSD Sym3T<T> rot_sym(T c, T s, const Sym3T<T>& S) {
   constexpr int i = (AX + 1) % 3, j = (AX + 2) % 3, k = AX;
-  Sym3 o;
-  float Sii = S.get<i, i>(), Sjj = S.get<j, j>(), Sij = S.get<i, j>(), Sik = S.get<i, k>(), Sjk = S.get<j, k>();
-  float cc = c * c, ss_ = s * s, cs = c * s;
-  o.at<k, k>() = S.get<k, k>();
-  o.at<i, k>() = c * Sik - s * Sjk;
-  o.at<j, k>() = s * Sik + c * Sjk;
-  float t = 2.f * cs * Sij;
-  o.at<i, i>() = cc * Sii - t + ss_ * Sjj;
-  o.at<j, j>() = ss_ * Sii + t + cc * Sjj;
-  o.at<i, j>() = cs * (Sii - Sjj) + (cc - ss_) * Sij;
+  Sym3T<T> o;
+  T Sii = S.template get<i, i>(), Sjj = S.template get<j, j>(), Sij = S.template get<i, j>(), Sik = S.template get<i, k>(),
+    Sjk = S.template get<j, k>();
+  T cc = c * c, ss_ = s * s, cs = c * s;
+  o.template at<k, k>() = S.template get<k, k>();
+  o.template at<i, k>() = c * Sik - s * Sjk;
+  o.template at<j, k>() = s * Sik + c * Sjk;
+  T t = (cs + cs) * Sij;
+  o.template at<i, i>() = cc * Sii - t + ss_ * Sjj;
+  o.template at<j, j>() = ss_ * Sii + t + cc * Sjj;
+  o.template at<i, j>() = cs * (Sii - Sjj) + (cc - ss_) * Sij;
   return o;
 }
 // M' = R M R^T for a general 3x3
-template <int AX>
-SSD void rot_gen(float c, float s, const float M[3][3], float O[3][3]) {
+template <int AX, class T>
+SSD void rot_gen(T c, T s, const T M[3][3], T O[3][3]) {
   constexpr int i = (AX + 1) % 3, j = (AX + 2) % 3, k = AX;
-  float T[3][3];
+  T Tm[3][3];
 #pragma unroll
   for (int col = 0; col < 3; ++col) {
-    T[i][col] = c * M[i][col] - s * M[j][col];
-    T[j][col] = s * M[i][col] + c * M[j][col];
-    T[k][col] = M[k][col];
+    Tm[i][col] = c * M[i][col] - s * M[j][col];
+    Tm[j][col] = s * M[i][col] + c * M[j][col];
+    Tm[k][col] = M[k][col];
   }
 #pragma unroll
   for (int row = 0; row < 3; ++row) {
-    O[row][i] = c * T[row][i] - s * T[row][j];
-    O[row][j] = s * T[row][i] + c * T[row][j];
-    O[row][k] = T[row][k];
+    O[row][i] = c * Tm[row][i] - s * Tm[row][j];
+    O[row][j] = s * Tm[row][i] + c * Tm[row][j];
+    O[row][k] = Tm[row][k];
   }
 }
 
 // articulated inertia of the child (in child coords) -> parent coords:  X^T I X
 //   rotate every block into the parent orientation, then shift the origin by r:
 //   C_p = C', B_p = B' + r x C' (column-wise), A_p[i][j] = A'[i][j] + (r x Bp_row_i)[j] + (r x B'_row_j)[i]
-template <class Model, int J>
-SSD ABI xinertia(float c, float s, const ABI& I) {
-  constexpr int AX = kAxis[J];
-  ABI o;
+template <class JT, class T>
+SSD ABIT<T> xinertia(T c, T s, const ABIT<T>& I) {
+  constexpr int AX = JT::AX;
+  ABIT<T> o;
   o.A = rot_sym<AX>(c, s, I.A);
   o.C = rot_sym<AX>(c, s, I.C);
-  float Bp[3][3];
+  T Bp[3][3];
   rot_gen<AX>(c, s, I.B, Bp);
-  if constexpr (has_offset<Model, J>()) {
+  if constexpr (JT::offset) {
     // r x B'_row_j for the three rows of B' (before the shift)
-    float rB[3][3];
+    T rB[3][3];
 #pragma unroll
-    for (int row = 0; row < 3; ++row) cross_r<Model, J>(Bp[row], rB[row]);
+    for (int row = 0; row < 3; ++row) JT::cross_r(Bp[row], rB[row]);
     // B_p = B' + r x C' column-wise (C' symmetric: column col = row col)
-    const Sym3& C = o.C;
-    float Cc[3][3] = {{C.m[0], C.m[3], C.m[4]}, {C.m[3], C.m[1], C.m[5]}, {C.m[4], C.m[5], C.m[2]}};
+    const Sym3T<T>& C = o.C;
+    T Cc[3][3] = {{C.m[0], C.m[3], C.m[4]}, {C.m[3], C.m[1], C.m[5]}, {C.m[4], C.m[5], C.m[2]}};
 #pragma unroll
     for (int col = 0; col < 3; ++col) {
-      float t[3];
-      cross_r<Model, J>(Cc[col], t);
+      T t[3];
+      JT::cross_r(Cc[col], t);
       Bp[0][col] += t[0]; Bp[1][col] += t[1]; Bp[2][col] += t[2];
     }
-    float rBp[3][3];
+    T rBp[3][3];
 #pragma unroll
-    for (int row = 0; row < 3; ++row) cross_r<Model, J>(Bp[row], rBp[row]);
+    for (int row = 0; row < 3; ++row) JT::cross_r(Bp[row], rBp[row]);
     o.A.m[0] += rBp[0][0] + rB[0][0];
     o.A.m[1] += rBp[1][1] + rB[1][1];
     o.A.m[2] += rBp[2][2] + rB[2][2];
@@ -259,6 +286,13 @@ SSD ABI xinertia(float c, float s, const ABI& I) {
     for (int b = 0; b < 3; ++b) o.B[a][b] = Bp[a][b];
   return o;
 }
+// the same three through scalar joint J by its number
+template <class Model, int J>
+SSD SV xmotion(float c, float s, const SV& p) { return xmotion<Joint<Model, J>>(c, s, p); }
+template <class Model, int J>
+SSD SV xforce(float c, float s, const SV& f) { return xforce<Joint<Model, J>>(c, s, f); }
+template <class Model, int J>
+SSD ABI xinertia(float c, float s, const ABI& I) { return xinertia<Joint<Model, J>>(c, s, I); }
 
 SSD void abi_add(ABI& a, const ABI& b) {
 #pragma unroll
@@ -270,6 +304,7 @@ SSD void abi_add(ABI& a, const ABI& b) {
 }
 
 // add the constexpr rigid-body inertia of body Bd:  A += I_O, B += m [c]x, C += m 1
+// (not merged with abi_add_bodyP: its constants are literal pairs, kept where either half is non-zero: another function of the model, not of T)
 template <class Model, int Bd>
 SSD void abi_add_body(ABI& I) {
   constexpr float m = Model::mass[Bd];
@@ -301,6 +336,7 @@ SSD ABI abi_body() {
 }
 
 // velocity-product bias force of a rigid body:  p = v x* (I_b v), constexpr inertia
+// (not merged with body_biasP: that one accumulates n and f in another order -- n[2], for one -- which rounds differently)
 template <class Model, int Bd>
 SSD SV body_bias(const SV& v) {
   constexpr float m = Model::mass[Bd];
@@ -375,28 +411,33 @@ SSD Chol6 chol6(const float M[6][6]) {
   });
   return L;
 }
-// x = -(L L^T)^-1 b   (the sign is what every caller needs)
-SSD SV chol6_solve_neg(const Chol6& L, const SV& b) {
-  float y[6] = {-b.w[0], -b.w[1], -b.w[2], -b.v[0], -b.v[1], -b.v[2]};
+// x = -(L L^T)^-1 b   (the sign is what every caller needs); T = ssf2: two right-hand sides at once.
+// The products are spelled l * y for float and y * l for ssf2, as the two former copies had them: the value is the same, the operand
+// order of the emitted fma is not, and either single spelling moves the step kernels' machine code (docs/HISTORY.md).
+template <class T>
+SSD SVT<T> chol6_solve_neg(const Chol6& L, const SVT<T>& b) {
+  T y[6] = {-b.w[0], -b.w[1], -b.w[2], -b.v[0], -b.v[1], -b.v[2]};
   static_for<0, 6>([&](auto Ic) {
     constexpr int i = decltype(Ic)::value;
-    float s = y[i];
+    T s = y[i];
     static_for<0, i>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value;
-      s -= L.template get<i, k>() * y[k];
+      if constexpr (std::is_same_v<T, float>) s -= L.template get<i, k>() * y[k];
+      else s -= y[k] * L.template get<i, k>();
     });
     y[i] = s * L.di[i];
   });
   static_rfor<5, 0>([&](auto Ic) {
     constexpr int i = decltype(Ic)::value;
-    float s = y[i];
+    T s = y[i];
     static_for<i + 1, 6>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value;
-      s -= L.template get<k, i>() * y[k];
+      if constexpr (std::is_same_v<T, float>) s -= L.template get<k, i>() * y[k];
+      else s -= y[k] * L.template get<k, i>();
     });
     y[i] = s * L.di[i];
   });
-  SV x;
+  SVT<T> x;
   x.w[0] = y[0]; x.w[1] = y[1]; x.w[2] = y[2]; x.v[0] = y[3]; x.v[1] = y[4]; x.v[2] = y[5];
   return x;
 }
