@@ -20,6 +20,11 @@
  *
  * Style: deliberately naive dense 6x6 spatial algebra, array-of-struct, one env at a time -- it shares no code
  * with the HIP kernels.  Build twice: -DSSO_REAL=float (parity) and -DSSO_REAL=double (drift characterisation).
+ *
+ * No state outside an env: the file has no non-const file-scope object.  What an env judges is its model (SSO_MODELS[kind], or
+ * the copy sso_create_model was given) and its sso_variant (the specification's SSO_SPEC unless sso_set_variant said otherwise);
+ * a step_ctx carries that variant and the call's instrumentation (decisions, contact_tap) down to the stages that read them, so
+ * envs of one process -- of both precision builds, on any thread -- cannot change what another one computes.
  */
 #include <math.h>
 #include <stdint.h>
@@ -49,7 +54,7 @@ typedef SSO_REAL real;
 #define STEP_RADIUS ((real)0.25)                    /* the reference's step_radius: scale of the step bonus (PHYSICS.md 4.5) */
 #define PGS_ITERS 5   /* PHYSICS.md 3.4 (Bullet's numSolverIterations = 5); rounds 1-4: 8 */
 #define PGS_WARM 1    /* warm start from the previous substep of the same control step; rounds 1-4: none */
-#define ERP ((real)0.2)
+#define ERP 0.2
 #define SLOP ((real)0.001)
 #define VCORR_MAX ((real)2.0)
 #define PI_D 3.14159265358979323846
@@ -203,15 +208,6 @@ typedef struct {
   float ep_ret_lo;   /* (double)ep_ret + (double)ep_ret_lo = the fp64 sum of the fp32 step rewards (include/steppingstone.h) */
 } sso_info;
 
-typedef struct {
-  int kind, num_envs, curriculum, auto_reset;
-  uint64_t seed;
-  int64_t env_offset;
-  real power;
-  const sso_model* M;
-  env_state* e;
-} sso_env;
-
 /* per-substep workspace (also exported to tests through sso_debug_*) */
 typedef struct {
   real X[NB][6][6], v[NB][6], c[NB][6], IA[NB][6][6], pA[NB][6], U[NB][6], Dinv[NB], u[NB], a[NB][6];
@@ -224,8 +220,8 @@ typedef struct {
  * discontinuously goes through decide(): class 0 = decisions that change the STATE (contact predicate of a sole
  * corner against a stone, winner among two touching stones, joint-limit switch), class 1 = decisions that only enter
  * reward / done (height, fall, posture bands, joint-at-limit count, target radius).  The sites are visited in a
- * data-independent order, so the running index of a site identifies it within a control step.  While g_dec points at
- * a `decisions` record the step
+ * data-independent order, so the running index of a site identifies it within a control step.  While the step context
+ * carries a `decisions` record the step
  *   - keeps, per class, the smallest distance of a decision to its threshold (metres / radians): margin[2];
  *   - lists the indices of the decisions that lie within `tol` of their threshold: near[], nnear;
  *   - inverts the outcome of the decisions listed in force[]: the "other branch" an fp32 implementation with a
@@ -242,10 +238,61 @@ typedef struct {
   real tol; int32_t* near; int nnear, cap;
   uint8_t* record; const uint8_t* replay; int ntrace;   /* outcome of decision idx written to / taken from [idx] */
 } decisions;
-static _Thread_local decisions* g_dec = 0;
+
+/* Contact-stage tap (tests only): when the step context carries one, contact_solve() copies its intermediate quantities out so
+ * that tests/np_contact.py can check every one of them against an independent fp64 numpy evaluation of PHYSICS.md 3.3-3.4. */
+typedef struct {
+  real Li[12][12], V0[12], W[8][3][6], bn[8], lam[8][3], nrm[8][3], pen[8];
+  real qdf[NJ], v0f[6], dqd[NJ], dv0[6];
+  int32_t active[8], stone[8];
+} contact_tap;
+
+/* The numbers of the specification that the studies under tools/ vary (never the parity tests).  A variant belongs to ONE env:
+ * sso_create installs SSO_SPEC, sso_set_variant another one (NULL: back to SSO_SPEC), between any two steps.  int32 / double in
+ * both precision builds, so that one ctypes mirror (tests/oracle_lib.py: Variant) serves them.
+ *   iters, warm        PHYSICS.md 3.4: sweeps; warm start from the previous substep of the same control step (rounds 1-4: 8, 0)
+ *   erp, seq_feet      Baumgarte factor; Gauss-Seidel instead of Jacobi BETWEEN the feet (a row then sees the other foot's
+ *                      impulses of the same sweep)
+ *   plank_a, plank_b   PHYSICS.md 3.3: half length / width of the stepping surface
+ *   stone_r            > 0: a DISC of that radius instead of the plank (rounds 1-5: 0.25 m, then 0.45 m)
+ *   dr_lo, dr_span     PHYSICS.md 6: stone spacing dr = dr_lo + u * dr_span * curriculum / 5
+ *   target_carried     1: a foot is on the target through a corner that stone n CARRIES; 0: the rounds-1-5 rule
+ *   target_r           > 0, with the rounds-1-5 rule: the corner must also lie within this radius of stone n's axis */
+typedef struct {
+  int32_t iters, warm, seq_feet, target_carried;
+  double erp, plank_a, plank_b, stone_r, dr_lo, dr_span, target_r;
+} sso_variant;
+static const sso_variant SSO_SPEC = {.iters = PGS_ITERS, .warm = PGS_WARM, .seq_feet = 0, .target_carried = 1, .erp = ERP,
+                                     .plank_a = SSO_PLANK_HALF_LENGTH, .plank_b = SSO_PLANK_HALF_WIDTH, .stone_r = 0,
+                                     .dr_lo = 0.65, .dr_span = 0.6, .target_r = 0};
+
+/* What one env-step reads beside the env: its variant in the build's precision, and the instrumentation of this call. */
+typedef struct {
+  int iters, warm, seq_feet, target_carried;
+  real erp, plank_a, plank_b, stone_r, dr_lo, dr_span, target_r;
+  decisions* dec;
+  contact_tap* tap;
+} step_ctx;
+static step_ctx make_ctx(const sso_variant* v, decisions* dec, contact_tap* tap) {
+  step_ctx cx = {v->iters, v->warm, v->seq_feet, v->target_carried, (real)v->erp, (real)v->plank_a, (real)v->plank_b,
+                 (real)v->stone_r, (real)v->dr_lo, (real)v->dr_span, (real)v->target_r, dec, tap};
+  return cx;
+}
+
+typedef struct {
+  int kind, num_envs, curriculum, auto_reset;
+  uint64_t seed;
+  int64_t env_offset;
+  real power;
+  const sso_model* M;     /* SSO_MODELS[kind], or own_model */
+  sso_model own_model;
+  sso_variant variant;
+  env_state* e;
+} sso_env;
+
 #define FAR_MARGIN ((real)1e30)
-static int decide(int which, int cond, real m) {
-  decisions* D = g_dec;
+static int decide(const step_ctx* cx, int which, int cond, real m) {
+  decisions* D = cx->dec;
   if (!D) return cond;
   int idx = D->seen++;
   if (m < 0) m = -m;
@@ -256,15 +303,6 @@ static int decide(int which, int cond, real m) {
   if (D->record && idx < D->ntrace) D->record[idx] = (uint8_t)(cond != 0);
   return cond;
 }
-
-/* Contact-stage tap (tests only): while g_tap is set, contact_solve() copies its intermediate quantities out so that
- * tests/np_contact.py can check every one of them against an independent fp64 numpy evaluation of PHYSICS.md 3.3-3.4. */
-typedef struct {
-  real Li[12][12], V0[12], W[8][3][6], bn[8], lam[8][3], nrm[8][3], pen[8];
-  real qdf[NJ], v0f[6], dqd[NJ], dv0[6];
-  int32_t active[8], stone[8];
-} contact_tap;
-static _Thread_local contact_tap* g_tap = 0;
 
 /* ------------------------------------------------------------------------------------------------ dynamics */
 static void kinematics(const sso_model* M, const env_state* s, work* w) {
@@ -285,12 +323,12 @@ static void kinematics(const sso_model* M, const env_state* s, work* w) {
 }
 
 /* PHYSICS.md 3.1 + 3.2.  tau_m: motor torques.  Outputs qdd[21], a0[6] (body coords, gravity included). */
-static void aba(const sso_model* M, const env_state* s, const real* tau_m, work* w, real* qdd, real* a0) {
+static void aba(const step_ctx* cx, const sso_model* M, const env_state* s, const real* tau_m, work* w, real* qdd, real* a0) {
   const real h = H_SUB;
   real tau[NJ], Dadd[NJ];
   for (int j = 0; j < NJ; ++j) {
     real q = s->q[j], qd = s->qd[j], viol = 0, kl = 0, dl = 0;
-    int over = decide(0, q > M->hi[j], q - M->hi[j]), under = decide(0, q < M->lo[j], q - M->lo[j]);
+    int over = decide(cx, 0, q > M->hi[j], q - M->hi[j]), under = decide(cx, 0, q < M->lo[j], q - M->lo[j]);
     if (over) viol = q - M->hi[j]; else if (under) viol = q - M->lo[j];
     if (over || under) { kl = M->klim[j]; dl = M->dlim[j]; }
     tau[j] = tau_m[j] - M->damping[j] * qd - M->stiffness[j] * (q + h * qd) - kl * (viol + h * qd) - dl * qd;
@@ -402,26 +440,15 @@ static void stone_normal(const real* st, real nrm[3]) {
 /* The stepping surface (PHYSICS.md 3.3, round 6): a PLANK whose footprint seen from above is 2 a x 2 b, aligned with the stone's heading
  * phi: with l the in-plane offset of the corner from the stone's centre, u = l_x cos(phi) + l_y sin(phi) along the heading and
  * v = l_y cos(phi) - l_x sin(phi) across it; inside when |u| < a and |v| < b.  a, b: SSO_PLANK_HALF_LENGTH / _WIDTH of the tables.
- * Study knobs (tools/sysid_policy.py ONLY; never the specification): another plank, a DISC of radius r instead (rounds 1-5: 0.25 m, then
- * 0.45 m), another stone spacing law, the rounds-1-5 on-target rule, an extra target radius (infinite-plane control). */
-static real g_plank_a = SSO_PLANK_HALF_LENGTH, g_plank_b = SSO_PLANK_HALF_WIDTH;
-void sso_debug_set_plank(double a, double b) { g_plank_a = a > 0 ? (real)a : SSO_PLANK_HALF_LENGTH; g_plank_b = a > 0 ? (real)b : SSO_PLANK_HALF_WIDTH; }
-static real g_stone_r = 0;      /* > 0: disc study mode */
-void sso_debug_set_stone_radius(double r) { g_stone_r = (real)r; }
-static real g_dr_lo = (real)0.65, g_dr_span = (real)0.6;
-void sso_debug_set_dr(double lo, double span) { g_dr_lo = (real)lo; g_dr_span = (real)span; }
-static int g_target_carried = 1;    /* 1 (specification): a foot is on the target through a corner that stone n CARRIES; 0: rounds 1-5 */
-static real g_target_r = 0;     /* > 0, with the rounds-1-5 rule: the corner must also lie within this radius of stone n's axis */
-void sso_debug_set_target_rule(int carried_only) { g_target_carried = carried_only; }
-void sso_debug_set_target_radius(double r) { g_target_r = (real)r; }
-static int plank_inside(const real* st, const real* l, real* margin) {
+ * The studies' other surfaces and rules are fields of sso_variant above. */
+static int plank_inside(const step_ctx* cx, const real* st, const real* l, real* margin) {
   real c = r_cos(st[3]), sn = r_sin(st[3]);
   real u = l[0] * c + l[1] * sn, v = l[1] * c - l[0] * sn;
-  real mu = g_plank_a - (u < 0 ? -u : u), mv = g_plank_b - (v < 0 ? -v : v);
+  real mu = cx->plank_a - (u < 0 ? -u : u), mv = cx->plank_b - (v < 0 ? -v : v);
   *margin = mu < mv ? mu : mv;
   return mu > 0 && mv > 0;
 }
-static void detect(const sso_model* M, const env_state* s, const work* w, contact ct[8], foot_report* fr) {
+static void detect(const step_ctx* cx, const sso_model* M, const env_state* s, const work* w, contact ct[8], foot_report* fr) {
   int n = s->n;
   int idx[3] = {n - 1 < 0 ? 0 : n - 1, n, n + 1 > NSTONE - 1 ? NSTONE - 1 : n + 1};
   for (int f = 0; f < 2; ++f) {
@@ -446,55 +473,45 @@ static void detect(const sso_model* M, const env_state* s, const work* w, contac
         real lx = dv[0] - d * nrm[0], ly = dv[1] - d * nrm[1], lz = dv[2] - d * nrm[2];
         real rho2 = lx * lx + ly * ly + lz * lz;
         real g1 = -d, g2 = d + (real)0.10, g3 = 0, l3[3] = {lx, ly, lz};
-        int inside = plank_inside(st, l3, &g3);
-        if (g_stone_r > 0) { inside = rho2 < g_stone_r * g_stone_r; g3 = g_stone_r - r_sqrt(rho2); }       /* disc study only */
+        int inside = plank_inside(cx, st, l3, &g3);
+        if (cx->stone_r > 0) { inside = rho2 < cx->stone_r * cx->stone_r; g3 = cx->stone_r - r_sqrt(rho2); }       /* disc study only */
         real gm = g1 < g2 ? g1 : g2;
         if (g3 < gm) gm = g3;
-        int touch = decide(0, d < 0 && d > (real)-0.10 && inside, gm);
+        int touch = decide(cx, 0, d < 0 && d > (real)-0.10 && inside, gm);
         /* rounds 1-5 (study only): on the target when a corner touches stone n, whichever stone carries that corner */
-        if (touch && sl == 1 && !g_target_carried && (g_target_r <= 0 || rho2 < g_target_r * g_target_r)) fr->foot_on_target[f] = 1;
+        if (touch && sl == 1 && !cx->target_carried && (cx->target_r <= 0 || rho2 < cx->target_r * cx->target_r)) fr->foot_on_target[f] = 1;
         /* two touching stones: the deeper one wins (a first touching stone always does, also when its predicate was
          * forced against d >= 0); an exact tie between COPLANAR stones goes to the stone visited first (n, n-1, n+1) and is not a decision -- either
          * winner gives the same normal and the same depth */
         int coplanar_tie = c->active && d == best && nrm[0] == c->n[0] && nrm[1] == c->n[1] && nrm[2] == c->n[2];
-        int wins = decide(0, !c->active || d < best, (touch && c->active && !coplanar_tie) ? d - best : FAR_MARGIN);
+        int wins = decide(cx, 0, !c->active || d < best, (touch && c->active && !coplanar_tie) ? d - best : FAR_MARGIN);
         if (touch && wins) {
           best = d; c->active = 1; c->stone = idx[sl]; c->pen = -d;
           c->n[0] = nrm[0]; c->n[1] = nrm[1]; c->n[2] = nrm[2];
         }
       }
       if (c->active) fr->foot_contact[f] = 1;
-      if (g_target_carried && c->active && c->stone == idx[1]) fr->foot_on_target[f] = 1;
+      if (cx->target_carried && c->active && c->stone == idx[1]) fr->foot_on_target[f] = 1;
     }
   }
 }
 
-/* solver knobs: PHYSICS.md 3.4 fixes them; sso_debug_set_solver() exists only for the convergence study of
- * tools/pgs_convergence.py */
-static int g_pgs_iters = PGS_ITERS;
-static int g_pgs_warm = PGS_WARM;
-void sso_debug_set_solver(int iters, int warm) { g_pgs_iters = iters; g_pgs_warm = warm; }
-/* further knobs of the same study (tools/spec_deviations.py -> docs/HISTORY.md section 3 table): Baumgarte factor, and
- * Gauss-Seidel instead of Jacobi BETWEEN the feet (a row then sees the other foot's impulses of the same sweep) */
-static real g_erp = ERP;
-static int g_seq_feet = 0;
-void sso_debug_set_variant(double erp, int seq_feet) { g_erp = (real)erp; g_seq_feet = seq_feet; }
-
 typedef struct { real lam[8][3]; int stone[8]; } warm_state;   /* impulses of the previous substep of this step */
 
 /* PHYSICS.md 3.3-3.4: returns dqd/dv0 to add to the free velocities */
-static void contact_solve(const sso_model* M, const work* w, const real* qd_free, const real* v0_free,
+static void contact_solve(const step_ctx* cx, const sso_model* M, const work* w, const real* qd_free, const real* v0_free,
                           contact ct[8], warm_state* ws, real* dqd, real* dv0) {
+  contact_tap* const tap = cx->tap;
   memset(dqd, 0, sizeof(real) * NJ);
   memset(dv0, 0, sizeof(real) * 6);
   int any = 0;
   for (int k = 0; k < 8; ++k) any |= ct[k].active;
-  if (g_tap) {
-    memset(g_tap, 0, sizeof *g_tap);
-    memcpy(g_tap->qdf, qd_free, sizeof(real) * NJ); memcpy(g_tap->v0f, v0_free, sizeof(real) * 6);
+  if (tap) {
+    memset(tap, 0, sizeof *tap);
+    memcpy(tap->qdf, qd_free, sizeof(real) * NJ); memcpy(tap->v0f, v0_free, sizeof(real) * 6);
     for (int k = 0; k < 8; ++k) {
-      g_tap->active[k] = ct[k].active; g_tap->stone[k] = ct[k].active ? ct[k].stone : -1; g_tap->pen[k] = ct[k].pen;
-      memcpy(g_tap->nrm[k], ct[k].n, sizeof(real) * 3);
+      tap->active[k] = ct[k].active; tap->stone[k] = ct[k].active ? ct[k].stone : -1; tap->pen[k] = ct[k].pen;
+      memcpy(tap->nrm[k], ct[k].n, sizeof(real) * 3);
     }
   }
   if (!any) { for (int k = 0; k < 8; ++k) ws->stone[k] = -1; return; }
@@ -520,7 +537,7 @@ static void contact_solve(const sso_model* M, const work* w, const real* qd_free
     vb[b][SSO_AXIS[j]] += qd_free[j];
   }
   for (int f = 0; f < 2; ++f) for (int k = 0; k < 6; ++k) V[f * 6 + k] = vb[foot_body[f]][k];
-  if (g_tap) memcpy(g_tap->V0, V, sizeof V);
+  if (tap) memcpy(tap->V0, V, sizeof V);
   /* rows */
   real W[8][3][6];
   real bn[8];
@@ -544,13 +561,13 @@ static void contact_solve(const sso_model* M, const work* w, const real* qd_free
     }
     real corr = c->pen - SLOP;
     if (corr < 0) corr = 0;
-    bn[k] = g_erp * corr / H_SUB;
+    bn[k] = cx->erp * corr / H_SUB;
     if (bn[k] > VCORR_MAX) bn[k] = VCORR_MAX;
     c->lam[0] = c->lam[1] = c->lam[2] = 0;
   }
   /* warm start: a corner that was in contact in the previous substep of this control step starts from that substep's
    * impulses (applied to the twists before the first sweep) */
-  if (g_pgs_warm)
+  if (cx->warm)
     for (int k = 0; k < 8; ++k) {
       contact* c = &ct[k];
       if (!c->active || ws->stone[k] < 0) continue;
@@ -562,7 +579,7 @@ static void contact_solve(const sso_model* M, const work* w, const real* qd_free
     }
   /* Gauss-Seidel inside each foot, Jacobi between the feet: during a sweep every row sees its own foot's twist
    * up to date, and the other foot's impulses of THIS sweep only once both feet have finished it. */
-  for (int it = 0; it < g_pgs_iters; ++it) {
+  for (int it = 0; it < cx->iters; ++it) {
     real Vnext[12];
     memcpy(Vnext, V, sizeof Vnext);
     for (int k = 0; k < 8; ++k) {
@@ -583,7 +600,7 @@ static void contact_solve(const sso_model* M, const work* w, const real* qd_free
           V[f * 6 + i] += y[f * 6 + i] * dl;          /* own foot: immediately (also tracked in Vnext) */
           Vnext[f * 6 + i] += y[f * 6 + i] * dl;
           Vnext[g * 6 + i] += y[g * 6 + i] * dl;      /* other foot: visible from the next sweep on */
-          if (g_seq_feet) V[g * 6 + i] += y[g * 6 + i] * dl;   /* (study variant: visible at once) */
+          if (cx->seq_feet) V[g * 6 + i] += y[g * 6 + i] * dl;   /* (study variant: visible at once) */
         }
       }
     }
@@ -602,27 +619,27 @@ static void contact_solve(const sso_model* M, const work* w, const real* qd_free
   }
   impulse_response(w, fimp, dvb, dqd);
   memcpy(dv0, dvb[0], sizeof(real) * 6);
-  if (g_tap) {
-    memcpy(g_tap->Li, Li, sizeof Li);
+  if (tap) {
+    memcpy(tap->Li, Li, sizeof Li);
     for (int k = 0; k < 8; ++k) {
       if (!ct[k].active) continue;
-      memcpy(g_tap->W[k], W[k], sizeof W[k]); g_tap->bn[k] = bn[k]; memcpy(g_tap->lam[k], ct[k].lam, sizeof(real) * 3);
+      memcpy(tap->W[k], W[k], sizeof W[k]); tap->bn[k] = bn[k]; memcpy(tap->lam[k], ct[k].lam, sizeof(real) * 3);
     }
-    memcpy(g_tap->dqd, dqd, sizeof(real) * NJ); memcpy(g_tap->dv0, dv0, sizeof(real) * 6);
+    memcpy(tap->dqd, dqd, sizeof(real) * NJ); memcpy(tap->dv0, dv0, sizeof(real) * 6);
   }
 }
 
-static void substep(const sso_model* M, env_state* s, const real* tau_m, foot_report* fr, warm_state* ws) {
+static void substep(const step_ctx* cx, const sso_model* M, env_state* s, const real* tau_m, foot_report* fr, warm_state* ws) {
   work w;
   const real h = H_SUB;
   real qdd[NJ], a0[6], qdf[NJ], v0f[6], dqd[NJ], dv0[6];
   contact ct[8];
   kinematics(M, s, &w);
-  aba(M, s, tau_m, &w, qdd, a0);
+  aba(cx, M, s, tau_m, &w, qdd, a0);
   for (int j = 0; j < NJ; ++j) qdf[j] = s->qd[j] + h * qdd[j];
   for (int i = 0; i < 6; ++i) v0f[i] = s->vel[i] + h * a0[i];
-  detect(M, s, &w, ct, fr);
-  contact_solve(M, &w, qdf, v0f, ct, ws, dqd, dv0);
+  detect(cx, M, s, &w, ct, fr);
+  contact_solve(cx, M, &w, qdf, v0f, ct, ws, dqd, dv0);
   for (int j = 0; j < NJ; ++j) { s->qd[j] = qdf[j] + dqd[j]; s->q[j] += h * s->qd[j]; }
   for (int i = 0; i < 6; ++i) s->vel[i] = v0f[i] + dv0[i];
   real vw[3];
@@ -677,12 +694,12 @@ static void place_stone(env_state* s, int k, real yaw, real pitch, real dr, real
 
 /* draw stone k from stone k-1 (PHYSICS.md section 6); returns dr.  Counterpart of env.sample_next_next_step() /
  * terrain_info[next_next_step, 0:6] = x,y,z,phi,x_tilt,y_tilt (playground/enjoy.py:52-64) */
-static real draw_stone(const sso_env* E, int e, env_state* s, int k) {
+static real draw_stone(const step_ctx* cx, const sso_env* E, int e, env_state* s, int k) {
   uint32_t r[4];
   env_block(E, e, s, r);
   int cell = sample_cell(s->prob, (float)(r[0] >> 8) * 5.9604644775390625e-08f);
   real ratio = (real)E->curriculum / (real)5;
-  real dr = g_dr_lo + u01(r[1]) * (g_dr_span * ratio);
+  real dr = cx->dr_lo + u01(r[1]) * (cx->dr_span * ratio);
   real tilt = (real)15.0 * DEG * ratio;
   real xt = (2 * u01(r[2]) - 1) * tilt, yt = (2 * u01(r[3]) - 1) * tilt;
   place_stone(s, k, yaw_sample(cell / NGRID), pitch_sample(cell % NGRID), dr, xt, yt);
@@ -770,7 +787,7 @@ static int state_finite(const env_state* s) {
 /* env.step(action) + the worker's auto-reset (common/envs_utils.py:645-649: terminal reward/done/info, RESET obs),
  * Monitor's episode statistics (:131-153), TimeLimitMask's bad_transition (:59-65), env.update_terrain
  * (playground/train.py:245); PHYSICS.md section 4 */
-static void env_step(const sso_env* E, int e, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info) {
+static void env_step(const step_ctx* cx, const sso_env* E, int e, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info) {
   const sso_model* M = E->M;
   env_state* s = &E->e[e];
   real a[NJ], tau[NJ];
@@ -781,7 +798,7 @@ static void env_step(const sso_env* E, int e, const float* act, float* obs, floa
   foot_report fr;
   warm_state ws;
   for (int k = 0; k < 8; ++k) ws.stone[k] = -1;
-  for (int k = 0; k < 4; ++k) substep(M, s, tau, &fr, &ws);
+  for (int k = 0; k < 4; ++k) substep(cx, M, s, tau, &fr, &ws);
   s->elapsed += 1;
   s->flags = (fr.foot_contact[0] ? 1 : 0) | (fr.foot_contact[1] ? 2 : 0);
   int finite = state_finite(s);
@@ -797,7 +814,7 @@ static void env_step(const sso_env* E, int e, const float* act, float* obs, floa
     }
     if (s->count >= 2 && s->n < NSTONE - 1) {
       s->n += 1; s->count = 0; advanced = 1;
-      if (s->n + 1 <= NSTONE - 1) s->nn_dr = draw_stone(E, e, s, s->n + 1);
+      if (s->n + 1 <= NSTONE - 1) s->nn_dr = draw_stone(cx, E, e, s, s->n + 1);
     }
   }
   /* 6. progress */
@@ -806,15 +823,15 @@ static void env_step(const sso_env* E, int e, const float* act, float* obs, floa
   s->pot_prev = advanced ? -planar_dist(s->terrain[s->n], s->pos) / DT_CTRL : pot;
   /* 7-8 */
   real dist_t = planar_dist(s->terrain[s->n], s->pos);
-  int inside = decide(1, dist_t < (real)0.15, s->n == NSTONE - 1 ? dist_t - (real)0.15 : FAR_MARGIN);
+  int inside = decide(cx, 1, dist_t < (real)0.15, s->n == NSTONE - 1 ? dist_t - (real)0.15 : FAR_MARGIN);
   real target_bonus = (s->n == NSTONE - 1 && inside) ? 2 : 0;
   real zs = fr.sole[0][2] < fr.sole[1][2] ? fr.sole[0][2] : fr.sole[1][2];
-  real tall_bonus = decide(1, s->pos[2] - zs > (real)0.7, s->pos[2] - zs - (real)0.7) ? 2 : -1;
+  real tall_bonus = decide(cx, 1, s->pos[2] - zs > (real)0.7, s->pos[2] - zs - (real)0.7) ? 2 : -1;
   int i0 = s->n - 1 < 0 ? 0 : s->n - 1, i2 = s->n + 1 > NSTONE - 1 ? NSTONE - 1 : s->n + 1;
   real zlow = s->terrain[i0][2];
   if (s->terrain[s->n][2] < zlow) zlow = s->terrain[s->n][2];
   if (s->terrain[i2][2] < zlow) zlow = s->terrain[i2][2];
-  int fell = decide(1, s->pos[2] < zlow + (real)0.3, s->pos[2] - zlow - (real)0.3);
+  int fell = decide(cx, 1, s->pos[2] < zlow + (real)0.3, s->pos[2] - zlow - (real)0.3);
   int d = tall_bonus < 0 || fell || !finite;
   int timeout = s->elapsed >= 1000;
   int bad = timeout; /* TimeLimitMask, common/envs_utils.py:59-65: done at the step limit, whatever else ended it */
@@ -825,8 +842,8 @@ static void env_step(const sso_env* E, int e, const float* act, float* obs, floa
   real posture = 0;
   real mp = pitch + (real)0.2 < (real)0.4 - pitch ? pitch + (real)0.2 : (real)0.4 - pitch;
   real mr = roll + (real)0.4 < (real)0.4 - roll ? roll + (real)0.4 : (real)0.4 - roll;
-  if (!decide(1, pitch > (real)-0.2 && pitch < (real)0.4, mp)) posture += r_abs(pitch);
-  if (!decide(1, roll > (real)-0.4 && roll < (real)0.4, mr)) posture += r_abs(roll);
+  if (!decide(cx, 1, pitch > (real)-0.2 && pitch < (real)0.4, mp)) posture += r_abs(pitch);
+  if (!decide(cx, 1, roll > (real)-0.4 && roll < (real)0.4, mr)) posture += r_abs(roll);
   real e_sum = 0, a2 = 0;
   int at_limit = 0;
   for (int j = 0; j < NJ; ++j) {
@@ -834,7 +851,7 @@ static void env_step(const sso_env* E, int e, const float* act, float* obs, floa
     a2 += a[j] * a[j];
     real mid = (real)0.5 * (M->lo[j] + M->hi[j]);
     real qn = r_abs(2 * (s->q[j] - mid) / (M->hi[j] - M->lo[j]));
-    if (decide(1, qn > (real)0.99, (qn - (real)0.99) * (real)0.5 * (M->hi[j] - M->lo[j]))) at_limit += 1;
+    if (decide(cx, 1, qn > (real)0.99, (qn - (real)0.99) * (real)0.5 * (M->hi[j] - M->lo[j]))) at_limit += 1;
   }
   real energy = ((real)4.5 / NJ) * (e_sum / NJ) + ((real)0.225 / NJ) * (a2 / NJ);
   real r = progress + step_bonus + target_bonus + tall_bonus - energy - posture - (real)0.1 * at_limit;
@@ -867,73 +884,41 @@ static void fill_window(float* prob, int c, int ring) {
   for (int k = 0; k < NCELL; ++k) prob[k] = prob[k] / (float)cnt;
 }
 
-/* Model override (tools/sysid_policy.py ONLY: the informational search over the specification's free numbers against the
- * reference's shipped policies).  Environments created AFTER the call use the given tables instead of the
- * compiled-in ones; no test and nothing in the package calls it, so the specification the parity tests judge is SSO_MODELS. */
-static sso_model g_model_override[2];
-static int g_model_overridden[2] = {0, 0};
-void sso_debug_set_model(int kind, const sso_model* m) {
-  if (kind < 0 || kind > 1) return;
-  if (m) { g_model_override[kind] = *m; g_model_overridden[kind] = 1; } else g_model_overridden[kind] = 0;
-}
 int sso_model_size(void) { return (int)sizeof(sso_model); }
+int sso_variant_size(void) { return (int)sizeof(sso_variant); }
 
-sso_env* sso_create(int kind, int num_envs, uint64_t seed, int64_t env_offset) {
+/* m: the env's own robot (copied; tools/sysid_policy.py ONLY, the informational search over the specification's free numbers
+ * against the reference's shipped policies).  NULL: the compiled-in SSO_MODELS[kind], which is what every test judges. */
+sso_env* sso_create_model(int kind, int num_envs, uint64_t seed, int64_t env_offset, const sso_model* m) {
   sso_env* E = (sso_env*)calloc(1, sizeof *E);
   E->kind = kind; E->num_envs = num_envs; E->seed = seed; E->env_offset = env_offset;
-  E->M = g_model_overridden[kind] ? &g_model_override[kind] : &SSO_MODELS[kind];
+  if (m) E->own_model = *m;
+  E->M = m ? &E->own_model : &SSO_MODELS[kind];
+  E->variant = SSO_SPEC;
   E->power = 1; E->curriculum = 0; E->auto_reset = 1;
   E->e = (env_state*)calloc((size_t)num_envs, sizeof(env_state));
   for (int e = 0; e < num_envs; ++e) { fill_window(E->e[e].prob, 0, 0); E->e[e].quat[0] = 1; }
   return E;
 }
+sso_env* sso_create(int kind, int num_envs, uint64_t seed, int64_t env_offset) { return sso_create_model(kind, num_envs, seed, env_offset, 0); }
 void sso_destroy(sso_env* E) { if (E) { free(E->e); free(E); } }
+void sso_spec_variant(sso_variant* out) { *out = SSO_SPEC; }
+void sso_get_variant(const sso_env* E, sso_variant* out) { *out = E->variant; }
+void sso_set_variant(sso_env* E, const sso_variant* v) { E->variant = v ? *v : SSO_SPEC; }
 void sso_reset(sso_env* E, float* obs) {
   for (int e = 0; e < E->num_envs; ++e) { env_reset(E, e); write_obs(E->M, &E->e[e], obs + (size_t)e * OBS_DIM); }
 }
-void sso_step(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info) {
-#pragma omp parallel for schedule(dynamic, 8)
-  for (int e = 0; e < E->num_envs; ++e)
-    env_step(E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
-}
-/* sso_step that also returns margins[N][2]: per env the smallest distance of a class-0 / class-1 decision of this
- * control step to its threshold (see decide() above) */
-void sso_step_margins(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info, real* margins) {
-#pragma omp parallel for schedule(dynamic, 8)
-  for (int e = 0; e < E->num_envs; ++e) {
-    decisions D;
-    memset(&D, 0, sizeof D);
-    margins[2 * e] = margins[2 * e + 1] = FAR_MARGIN;
-    D.margin = margins + 2 * e;
-    g_dec = &D;
-    env_step(E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
-    g_dec = 0;
-  }
-}
-/* sso_step_margins that also lists, per env, the indices of the decisions within `tol` of their threshold:
- * near[N][cap] (first cap of them) and nnear[N] (their true number, which may exceed cap) */
-void sso_step_near(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info, real* margins,
-                   double tol, int32_t* near, int32_t* nnear, int cap) {
-#pragma omp parallel for schedule(dynamic, 8)
-  for (int e = 0; e < E->num_envs; ++e) {
-    decisions D;
-    memset(&D, 0, sizeof D);
-    margins[2 * e] = margins[2 * e + 1] = FAR_MARGIN;
-    D.margin = margins + 2 * e;
-    D.tol = (real)tol; D.near = near + (size_t)e * cap; D.cap = cap;
-    g_dec = &D;
-    env_step(E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
-    g_dec = 0;
-    nnear[e] = D.nnear;
-  }
-}
-/* The general form: any of margins [N][2], near [N][cap] + nnear [N], force [N][cap] + nforce [N], record [N][ntrace],
- * replay [N][ntrace] may be null.  SSO_MAX_DECISIONS bounds the number of decision sites of a control step. */
+/* The one step loop.  Any of margins [N][2] (per env the smallest distance of a class-0 / class-1 decision of this control step
+ * to its threshold, see decide() above; alone if that is all that is asked for), near [N][cap] + nnear [N] (the decisions within
+ * `tol` of their threshold: the first cap indices, and their true number), force [N][cap] + nforce [N] (decisions whose outcome
+ * is inverted), record [N][ntrace], replay [N][ntrace] may be null; with all of them null it is sso_step.  SSO_MAX_DECISIONS
+ * bounds the number of decision sites of a control step. */
 #define SSO_MAX_DECISIONS 400
 int sso_max_decisions(void) { return SSO_MAX_DECISIONS; }
 void sso_step_ex(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info, real* margins, double tol,
                  int32_t* near, int32_t* nnear, const int32_t* force, const int32_t* nforce, int cap, uint8_t* record,
                  const uint8_t* replay, int ntrace) {
+  const int plain = !margins && !near && !force && !record && !replay;
 #pragma omp parallel for schedule(dynamic, 8)
   for (int e = 0; e < E->num_envs; ++e) {
     decisions D;
@@ -944,24 +929,13 @@ void sso_step_ex(sso_env* E, const float* act, float* obs, float* rew, uint8_t* 
     D.ntrace = ntrace;
     if (record) D.record = record + (size_t)e * ntrace;
     if (replay) D.replay = replay + (size_t)e * ntrace;
-    g_dec = &D;
-    env_step(E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
-    g_dec = 0;
+    const step_ctx cx = make_ctx(&E->variant, plain ? 0 : &D, 0);
+    env_step(&cx, E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
     if (nnear) nnear[e] = D.nnear;
   }
 }
-/* sso_step with, per env, the outcome of the decisions force[e][0 .. nforce[e]) inverted */
-void sso_step_forced(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info,
-                     const int32_t* force, const int32_t* nforce, int cap) {
-#pragma omp parallel for schedule(dynamic, 8)
-  for (int e = 0; e < E->num_envs; ++e) {
-    decisions D;
-    memset(&D, 0, sizeof D);
-    D.force = force + (size_t)e * cap; D.nforce = nforce[e];
-    g_dec = &D;
-    env_step(E, e, act + (size_t)e * NJ, obs + (size_t)e * OBS_DIM, rew + e, done + e, info + e);
-    g_dec = 0;
-  }
+void sso_step(sso_env* E, const float* act, float* obs, float* rew, uint8_t* done, sso_info* info) {
+  sso_step_ex(E, act, obs, rew, done, info, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
 }
 void sso_set_curriculum(sso_env* E, int c) {
   E->curriculum = c;
@@ -1048,9 +1022,10 @@ int sso_state_dim(void) { return STATE_DIM; }
 void sso_debug_aba(int kind, const real* packed, const real* tau_m, real* qdd, real* a0) {
   sso_env* E = sso_create(kind, 1, 0, 0);
   sso_set_state(E, packed);
-  static work w;
+  const step_ctx cx = make_ctx(&E->variant, 0, 0);
+  work w;
   kinematics(E->M, &E->e[0], &w);
-  aba(E->M, &E->e[0], tau_m, &w, qdd, a0);
+  aba(&cx, E->M, &E->e[0], tau_m, &w, qdd, a0);
   sso_destroy(E);
 }
 /* n substeps with fixed motor torques; state in/out; last foot report out (2 contact flags, 2 target flags) */
@@ -1059,7 +1034,8 @@ void sso_debug_substeps(sso_env* E, int e, const real* tau_m, int n, int* flags4
   warm_state ws;
   memset(&fr, 0, sizeof fr);
   for (int k = 0; k < 8; ++k) ws.stone[k] = -1;
-  for (int k = 0; k < n; ++k) substep(E->M, &E->e[e], tau_m, &fr, &ws);
+  const step_ctx cx = make_ctx(&E->variant, 0, 0);
+  for (int k = 0; k < n; ++k) substep(&cx, E->M, &E->e[e], tau_m, &fr, &ws);
   flags4[0] = fr.foot_contact[0]; flags4[1] = fr.foot_contact[1];
   flags4[2] = fr.foot_on_target[0]; flags4[3] = fr.foot_on_target[1];
 }
@@ -1071,18 +1047,16 @@ void sso_debug_contact_after(sso_env* E, int e, const real* tau_m, int prior, co
   warm_state ws;
   memset(&fr, 0, sizeof fr);
   for (int k = 0; k < 8; ++k) ws.stone[k] = -1;
-  for (int k = 0; k < prior; ++k) substep(E->M, &E->e[e], tau_m, &fr, &ws);
-  g_tap = tap;
-  substep(E->M, &E->e[e], tau_m, &fr, &ws);
-  g_tap = 0;
+  const step_ctx plain = make_ctx(&E->variant, 0, 0), tapped = make_ctx(&E->variant, 0, tap);
+  for (int k = 0; k < prior; ++k) substep(&plain, E->M, &E->e[e], tau_m, &fr, &ws);
+  substep(&tapped, E->M, &E->e[e], tau_m, &fr, &ws);
 }
-void sso_debug_contact(sso_env* E, int e, const real* tau_m, contact_tap* tap) { sso_debug_contact_after(E, e, tau_m, 0, tap); }
 int sso_tap_size(void) { return (int)sizeof(contact_tap); }
 /* world position of every body (22 x 3) and rotation (22 x 9) for FK checks */
 void sso_debug_fk(int kind, const real* packed, real* pos, real* rot) {
   sso_env* E = sso_create(kind, 1, 0, 0);
   sso_set_state(E, packed);
-  static work w;
+  work w;
   kinematics(E->M, &E->e[0], &w);
   for (int b = 0; b < NB; ++b) {
     for (int i = 0; i < 3; ++i) pos[b * 3 + i] = w.pw[b][i];

@@ -27,6 +27,12 @@ class Info(C.Structure):
                 ("steps_reached", C.c_int32), ("update_terrain", C.c_int32), ("ep_ret_lo", C.c_float)]
 
 
+class Variant(C.Structure):
+    """oracle/ss_oracle.c: sso_variant, the numbers of the specification a study may vary on ONE env (same layout in both builds)"""
+    _fields_ = [(k, C.c_int32) for k in ("iters", "warm", "seq_feet", "target_carried")] + \
+               [(k, C.c_double) for k in ("erp", "plank_a", "plank_b", "stone_r", "dr_lo", "dr_span", "target_r")]
+
+
 INFO_DTYPE = np.dtype([("ep_ret", "f4"), ("ep_len", "f4"), ("bad_transition", "i4"), ("steps_reached", "i4"),
                        ("update_terrain", "i4"), ("ep_ret_lo", "f4")])
 
@@ -54,14 +60,16 @@ def load(prec="f32"):
     vp, i32, u64, i64, dbl = C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_double
     lib.sso_create.restype = vp
     lib.sso_create.argtypes = [i32, i32, u64, i64]
+    lib.sso_create_model.restype = vp
+    lib.sso_create_model.argtypes = [i32, i32, u64, i64, vp]
+    lib.sso_spec_variant.argtypes = [vp]
+    lib.sso_get_variant.argtypes = [vp, vp]
+    lib.sso_set_variant.argtypes = [vp, vp]
+    assert lib.sso_variant_size() == C.sizeof(Variant), "sso_variant layout changed"
     lib.sso_destroy.argtypes = [vp]
     lib.sso_reset.argtypes = [vp, vp]
     lib.sso_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.sso_step_margins.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.sso_step_near.argtypes = [vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, i32]
-    lib.sso_step_forced.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32]
     lib.sso_step_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, i32, vp, vp, i32]
-    lib.sso_debug_contact.argtypes = [vp, i32, vp, vp]
     lib.sso_debug_contact_after.argtypes = [vp, i32, vp, i32, vp]
     lib.sso_set_curriculum.argtypes = [vp, i32]
     lib.sso_set_specialist.argtypes = [vp, i32]
@@ -88,12 +96,18 @@ def _p(a):
 class OracleEnv:
     """Batched oracle env with the same call surface as the C-ABI handle (numpy in/out)."""
 
-    def __init__(self, kind="walker3d", num_envs=1, seed=0, env_offset=0, prec="f32"):
+    def __init__(self, kind="walker3d", num_envs=1, seed=0, env_offset=0, prec="f32", model=None, variant=None):
+        """model: a ctypes mirror of sso_model (tools/sysid_policy.py: SsoModel) that this env copies; variant: a dict of
+        Variant fields that differ from the specification.  Both belong to this env alone; None is the specification."""
         self.lib = load(prec)
         self.real = np.float32 if prec == "f32" else np.float64
         self.kind = KIND[kind] if isinstance(kind, str) else int(kind)
         self.n = int(num_envs)
-        self.h = self.lib.sso_create(self.kind, self.n, int(seed), int(env_offset))
+        if model is not None:
+            assert C.sizeof(model) == self.lib.sso_model_size(), "sso_model layout changed"
+        self.h = self.lib.sso_create_model(self.kind, self.n, int(seed), int(env_offset), None if model is None else C.addressof(model))
+        if variant:
+            self.set_variant(**variant)
 
     def close(self):
         if self.h:
@@ -124,52 +138,26 @@ class OracleEnv:
         """step() that also returns margins [N,2]: the distance of the closest discrete decision of this control step
         to its threshold -- column 0: decisions that change the state (contact set, stone choice, joint-limit
         switches; metres / radians), column 1: decisions that only enter reward / done."""
-        act = np.ascontiguousarray(act, np.float32).reshape(self.n, ACT_DIM)
-        obs = np.zeros((self.n, OBS_DIM), np.float32)
-        rew = np.zeros(self.n, np.float32)
-        done = np.zeros(self.n, np.uint8)
-        info = np.zeros(self.n, INFO_DTYPE)
-        margins = np.zeros((self.n, 2), self.real)
-        self.lib.sso_step_margins(self.h, _p(act), _p(obs), _p(rew), _p(done), _p(info), _p(margins))
-        return obs, rew, done, info, margins
+        r = self.step_ex(act, margins=True)
+        return r["obs"], r["rew"], r["done"], r["info"], r["margins"]
 
     def _out(self):
         return (np.zeros((self.n, OBS_DIM), np.float32), np.zeros(self.n, np.float32), np.zeros(self.n, np.uint8),
                 np.zeros(self.n, INFO_DTYPE))
 
-    def step_near(self, act, tol=1e-5, cap=NEAR_CAP):
-        """step_margins() that also lists the decisions within `tol` of their threshold: near [N,cap] (indices of the
-        decision sites in visiting order, -1 padded) and nnear [N] (their true number; > cap means the list is cut)."""
-        act = np.ascontiguousarray(act, np.float32).reshape(self.n, ACT_DIM)
-        obs, rew, done, info = self._out()
-        margins = np.zeros((self.n, 2), self.real)
-        near = np.full((self.n, cap), -1, np.int32)
-        nnear = np.zeros(self.n, np.int32)
-        self.lib.sso_step_near(self.h, _p(act), _p(obs), _p(rew), _p(done), _p(info), _p(margins), float(tol), _p(near),
-                               _p(nnear), int(cap))
-        return obs, rew, done, info, margins, near, nnear
-
-    def step_forced(self, act, force, nforce):
-        """step() with, per env, the outcome of the decisions force[e, :nforce[e]] inverted (the other branch of a
-        near-threshold decision)."""
-        act = np.ascontiguousarray(act, np.float32).reshape(self.n, ACT_DIM)
-        force = np.ascontiguousarray(force, np.int32).reshape(self.n, -1)
-        nforce = np.ascontiguousarray(nforce, np.int32).reshape(self.n)
-        obs, rew, done, info = self._out()
-        self.lib.sso_step_forced(self.h, _p(act), _p(obs), _p(rew), _p(done), _p(info), _p(force), _p(nforce), force.shape[1])
-        return obs, rew, done, info
-
-    def step_ex(self, act, tol=None, cap=NEAR_CAP, force=None, nforce=None, record=False, replay=None):
-        """The general step: returns a dict with obs / rew / done / info and, on request, `margins` [N,2] + `near`
-        [N,cap] + `nnear` [N] (tol given: decisions within tol of their threshold), `trace` [N,MAX_DECISIONS] uint8
-        (record=True: the outcome of every decision).  force / nforce invert the listed decisions; replay (a trace)
-        freezes every decision to the recorded outcome."""
+    def step_ex(self, act, tol=None, cap=NEAR_CAP, force=None, nforce=None, record=False, replay=None, margins=False):
+        """The general step: returns a dict with obs / rew / done / info and, on request, `margins` [N,2] (margins=True, or
+        tol given) + `near` [N,cap] + `nnear` [N] (tol given: decisions within tol of their threshold), `trace`
+        [N,MAX_DECISIONS] uint8 (record=True: the outcome of every decision).  force / nforce invert the listed decisions;
+        replay (a trace) freezes every decision to the recorded outcome."""
         act = np.ascontiguousarray(act, np.float32).reshape(self.n, ACT_DIM)
         obs, rew, done, info = self._out()
         out = dict(obs=obs, rew=rew, done=done, info=info)
-        margins = near = nnear = trace = None
+        near = nnear = trace = None
+        margins = np.zeros((self.n, 2), self.real) if margins or tol is not None else None
+        if margins is not None:
+            out["margins"] = margins
         if tol is not None:
-            margins = out["margins"] = np.zeros((self.n, 2), self.real)
             near = out["near"] = np.full((self.n, cap), -1, np.int32)
             nnear = out["nnear"] = np.zeros(self.n, np.int32)
         if force is not None:
@@ -193,6 +181,21 @@ class OracleEnv:
         assert tap.nbytes == self.lib.sso_tap_size()
         self.lib.sso_debug_contact_after(self.h, int(e), _p(tau), int(prior), _p(tap))
         return {k: tap[k][0].copy() for k in tap.dtype.names}
+
+    def set_variant(self, **fields):
+        """This env judges the specification with `fields` (of Variant) changed, from its next step on; no fields: the
+        specification again."""
+        v = Variant()
+        self.lib.sso_spec_variant(C.addressof(v))
+        for k, x in fields.items():
+            assert k in dict(Variant._fields_), k
+            setattr(v, k, x)
+        self.lib.sso_set_variant(self.h, C.addressof(v) if fields else None)
+
+    def variant(self):
+        v = Variant()
+        self.lib.sso_get_variant(self.h, C.addressof(v))
+        return {k: getattr(v, k) for k, _ in Variant._fields_}
 
     def set_curriculum(self, c):
         self.lib.sso_set_curriculum(self.h, int(c))
@@ -241,6 +244,13 @@ class OracleEnv:
         flags = np.zeros(4, np.int32)
         self.lib.sso_debug_substeps(self.h, int(e), _p(tau), int(n), _p(flags))
         return flags
+
+
+def spec_variant(prec="f32"):
+    """The specification's own Variant fields (PHYSICS.md 3.3 / 3.4 / 6), as a dict."""
+    v = Variant()
+    load(prec).sso_spec_variant(C.addressof(v))
+    return {k: getattr(v, k) for k, _ in Variant._fields_}
 
 
 def philox(ctr, key):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """INFORMATIONAL (this container only; never a parity claim, nothing here changes the specification): how the survival of the reference's
-SHIPPED deterministic policies in our env responds to the free numbers of docs/PHYSICS.md -- solver knobs (run-time debug hooks of the
-oracle) and global scale factors of the robot model (a private copy of the oracle built with regenerated tables under var/scan/; the
+SHIPPED deterministic policies in our env responds to the free numbers of docs/PHYSICS.md -- solver knobs (the oracle's per-env variant, relative to
+the rounds-1-4 solve: 8 cold sweeps) and global scale factors of the robot model (a private copy of the oracle built with regenerated tables under var/scan/; the
 tree's tables and libraries are not touched).  A parameter whose change multiplies the survival time of BOTH policies is where our
 robot differs most from the one they were trained on.
 
@@ -27,13 +27,7 @@ solver = %(solver)r
 out = []
 for kind, f in (("walker3d", "mocca_envs:Walker3DStepperEnv-v0_latest.pt"), ("mike", "mocca_envs:MikeStepperEnv-v0_latest.pt")):
     actor = load_reference_checkpoint(M + f).actor
-    o = ol.OracleEnv(kind, 128, seed=9)
-    if solver:
-        import ctypes as C
-        o.lib.sso_debug_set_solver.argtypes = [C.c_int, C.c_int]
-        o.lib.sso_debug_set_variant.argtypes = [C.c_double, C.c_int]
-        o.lib.sso_debug_set_solver(int(solver.get("iters", 8)), int(solver.get("warm", 0)))
-        o.lib.sso_debug_set_variant(float(solver.get("erp", 0.2)), int(solver.get("seq", 0)))
+    o = ol.OracleEnv(kind, 128, seed=9, variant=dict(dict(iters=8, warm=0), **solver) if solver else None)
     o.set_curriculum(0)
     obs = o.reset()
     lens, reached = [], []
@@ -95,7 +89,7 @@ def main():
     print("%-46s %s" % ("specification as it is", run()))
     for label, s in (("PGS sweeps 5 (SURVEY 9: numSolverIterations)", dict(iters=5)), ("PGS sweeps 16", dict(iters=16)), ("PGS sweeps 32", dict(iters=32)),
                      ("warm start from the previous substep", dict(warm=1)), ("ERP 0.5", dict(erp=0.5)), ("ERP 0.9 (SURVEY 9)", dict(erp=0.9)),
-                     ("Gauss-Seidel across the feet", dict(seq=1)), ("5 sweeps + warm start + ERP 0.9 (SURVEY 9 altogether)", dict(iters=5, warm=1, erp=0.9))):
+                     ("Gauss-Seidel across the feet", dict(seq_feet=1)), ("5 sweeps + warm start + ERP 0.9 (SURVEY 9 altogether)", dict(iters=5, warm=1, erp=0.9))):
         print("%-46s %s" % (label, run(solver=s)), flush=True)
     if "--solver-only" in sys.argv:
         return

@@ -12,7 +12,7 @@ that by +-15 steps.  This tool searches ALL free numbers of steppingstone_amd/mo
 
 and maximises, over 64 envs on flat terrain from the reset distribution, the mean number of stones the deterministic shipped actor
 reaches (+ a small credit for staying up).  Candidates are evaluated in worker processes on private model tables handed to the
-oracle through sso_debug_set_model (the compiled-in specification is untouched).
+oracle env that evaluates them (OracleEnv(model=...); the compiled-in specification and every other env are untouched).
 
   python tools/sysid_policy.py --kind walker3d --generations 400 --out profiles/r05_sysid_walker3d
   python tools/sysid_policy.py --kind walker3d --evaluate profiles/r05_sysid_walker3d_best.json      # re-score a result on other seeds / terrain
@@ -225,9 +225,6 @@ def _init_worker(kind):
     import oracle_lib as ol
     from steppingstone_amd.legacy_checkpoint import load_reference_checkpoint
     _W["ol"] = ol
-    _W["lib"] = ol.load("f32")
-    _W["lib"].sso_debug_set_model.argtypes = [C.c_int, C.c_void_p]
-    assert _W["lib"].sso_model_size() == C.sizeof(SsoModel), "sso_model layout changed"
     _W["actor"] = load_reference_checkpoint(MODELS + POLICY[kind]).actor
     _W["actors"] = {"latest": _W["actor"]}
     for key, f in POLICY_ALT.items():
@@ -239,9 +236,10 @@ def _init_worker(kind):
 
 def rollout(kind, ov, n=64, steps=500, seed=9, curriculum=0, detail=False, policy="latest", env=None, use_identified=False):
     """deterministic shipped actor in the oracle with model overrides `ov`: first episode of each of n envs.  `env`: terrain / contact
-    study knobs of the ORACLE only (plank=(a, b), dr=(lo, span), target_carried=0/1, stone_radius)."""
+    study knobs of the ORACLE only (plank=(a, b), dr=(lo, span), target_carried=0/1, target_radius, stone_radius), which become fields
+    of that one env's variant."""
     from steppingstone_amd import model
-    ol, lib, torch = _W["ol"], _W["lib"], _W["torch"]
+    ol, torch = _W["ol"], _W["torch"]
     actor = _W["actors"][policy]
     ov = dict(ov)
     env = dict(env or {})
@@ -250,25 +248,20 @@ def rollout(kind, ov, n=64, steps=500, seed=9, curriculum=0, detail=False, polic
     plank = ov.pop("env.plank", None)
     if plank is not None and "plank" not in env and "stone_radius" not in env:
         env["plank"] = plank
-    lib.sso_debug_set_stone_radius.argtypes = [C.c_double]
-    lib.sso_debug_set_plank.argtypes = [C.c_double, C.c_double]
-    lib.sso_debug_set_dr.argtypes = [C.c_double, C.c_double]
     # round 6: the specification's stepping surface is the PLANK of the tables; a stone radius (a rounds-1-5 search space, a disc
     # variant of the scan) switches the oracle to its disc study mode
-    lib.sso_debug_set_stone_radius(float(stone_r) if (stone_r is not None and "plank" not in env) else 0.0)
-    lib.sso_debug_set_plank(*[float(v) for v in env.get("plank", (0.0, 0.0))])
-    lib.sso_debug_set_dr(*[float(v) for v in env.get("dr", (0.65, 0.6))])
-    lib.sso_debug_set_target_rule(int(env.get("target_carried", TARGET_CARRIED)))
-    lib.sso_debug_set_target_radius.argtypes = [C.c_double]
-    lib.sso_debug_set_target_radius(float(env.get("target_radius", 0.0)))
+    variant = dict(target_carried=int(env.get("target_carried", TARGET_CARRIED)), target_r=float(env.get("target_radius", 0.0)))
+    if stone_r is not None and "plank" not in env:
+        variant["stone_r"] = float(stone_r)
+    if "plank" in env:
+        variant["plank_a"], variant["plank_b"] = (float(v) for v in env["plank"])
+    if "dr" in env:
+        variant["dr_lo"], variant["dr_span"] = (float(v) for v in env["dr"])
     try:
         m = model.build(kind, ov, use_identified=use_identified)        # the search is relative to the rounds-1-4 prior
     except Exception:
         return (-1.0, {}) if detail else -1.0
-    sm = pack_model(m)
-    lib.sso_debug_set_model(ol.KIND[kind], C.byref(sm))
-    o = ol.OracleEnv(kind, n, seed=seed)
-    lib.sso_debug_set_model(ol.KIND[kind], None)        # the env keeps its pointer to a static copy; later envs are not affected
+    o = ol.OracleEnv(kind, n, seed=seed, model=pack_model(m), variant=variant)
     if curriculum:
         o.set_curriculum(curriculum)
     obs = o.reset()

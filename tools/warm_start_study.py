@@ -8,7 +8,7 @@ from a converged contact solve (400 cold sweeps per substep) for sweep counts x 
 
 "cross" exists only here: the tool builds a private copy of oracle/ss_oracle.c in a temp directory and patches a persistent warm
 state into it (the repository's oracle is not touched).   python tools/warm_start_study.py > profiles/r05_warm_start_study.txt"""
-import ctypes as C, os, subprocess, sys, tempfile
+import ctypes as C, os, subprocess, sys, tempfile     # ctypes: only for the entry points this tool patches in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMP = tempfile.mkdtemp(prefix="ss_warm_study_")
 s = open(os.path.join(ROOT, "oracle", "ss_oracle.c")).read()
@@ -26,11 +26,11 @@ void sso_debug_set_warm_factor(double f) { g_warm_factor = (real)f; }""")
 rep("""        c->lam[d] = ws->lam[k][d];""", """        c->lam[d] = g_warm_factor * ws->lam[k][d];""")
 rep("""  warm_state ws;
   for (int k = 0; k < 8; ++k) ws.stone[k] = -1;
-  for (int k = 0; k < 4; ++k) substep(M, s, tau, &fr, &ws);""", """  warm_state ws;
+  for (int k = 0; k < 4; ++k) substep(cx, M, s, tau, &fr, &ws);""", """  warm_state ws;
   for (int k = 0; k < 8; ++k) ws.stone[k] = -1;
-  if (g_pgs_warm == 2) ws = g_wsp[e];
-  for (int k = 0; k < 4; ++k) substep(M, s, tau, &fr, &ws);
-  if (g_pgs_warm == 2) g_wsp[e] = ws;""")
+  if (cx->warm == 2) ws = g_wsp[e];
+  for (int k = 0; k < 4; ++k) substep(cx, M, s, tau, &fr, &ws);
+  if (cx->warm == 2) g_wsp[e] = ws;""")
 rep("""  E->e = (env_state*)calloc((size_t)num_envs, sizeof(env_state));""", """  E->e = (env_state*)calloc((size_t)num_envs, sizeof(env_state));
   g_wsp = (warm_state*)calloc((size_t)num_envs, sizeof(warm_state)); g_wsp_n = num_envs;
   for (int e = 0; e < num_envs; ++e) for (int k = 0; k < 8; ++k) g_wsp[e].stone[k] = -1;""")
@@ -46,7 +46,6 @@ os.environ["SS_ORACLE_LIB_F64"] = os.path.join(TMP, "liboracle_f64.so")
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np, oracle_lib as ol
 lib=ol.load("f64")
-lib.sso_debug_set_solver.argtypes=[C.c_int,C.c_int]
 lib.sso_debug_get_warm.argtypes=[C.c_void_p]; lib.sso_debug_set_warm.argtypes=[C.c_void_p]
 lib.sso_debug_set_warm_factor.argtypes=[C.c_double]
 n=64
@@ -56,14 +55,14 @@ def getw():
 def setw(b): lib.sso_debug_set_warm(b.ctypes.data_as(C.c_void_p))
 for label, amp in (("random actions (x1.0 / x0.3 alternating)", None), ("small actions x0.15 (standing / swaying)", 0.15)):
     o=ol.OracleEnv("walker3d",n,seed=1,prec="f64"); o.reset()
-    lib.sso_debug_set_solver(5,2); lib.sso_debug_set_warm_factor(1.0)
+    o.set_variant(iters=5,warm=2); lib.sso_debug_set_warm_factor(1.0)
     states,acts,warms=[],[],[]
     for t in range(60):
         a=o.random_actions(t)*((0.3 if t%2 else 1.0) if amp is None else amp)
         states.append(o.get_state().copy()); acts.append(a); warms.append(getw())
         o.step(a)
     def run(iters,warm,factor=1.0):
-        lib.sso_debug_set_solver(iters,warm); lib.sso_debug_set_warm_factor(factor)
+        o.set_variant(iters=iters,warm=warm); lib.sso_debug_set_warm_factor(factor)
         out=[]
         for st,a,w in zip(states,acts,warms):
             o.set_state(st); o.set_auto_reset(False); setw(w)
