@@ -98,6 +98,25 @@ def build_fuzz(force=False, verbose=False):
     return _compile_lib(FUZZ_LIB, ["-DSS_FUZZ_SCHED"], "_fuzz", verbose)
 
 
+PROBE_LIB = os.path.join(LIBDIR, "libss_probe.so")
+PROBE_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe.hip")
+
+
+def build_probe(force=False, verbose=False):
+    """lib/libss_probe.so from tests/device/ss_probe.hip: the spatial algebra of ss_math.hpp / ss_pair.hpp / ss_dynamics.hpp behind one
+    C entry, one operator per launch, compiled with the product's FLAGS (so the operators round as they do inside the step kernels).
+    TEST BUILD -- tests/test_spatial_ops.py holds every operator against an fp64 reference; nothing in the package loads it."""
+    deps = [PROBE_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and os.path.exists(PROBE_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_LIB) for d in deps if os.path.exists(d)):
+        return PROBE_LIB
+    os.makedirs(LIBDIR, exist_ok=True)
+    cmd = [hipcc()] + FLAGS + ["-shared", PROBE_SRC, "-o", PROBE_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return PROBE_LIB
+
+
 def build_variant(name, extra_flags, verbose=False):
     """var/libss_<name>.so: the product recipe plus extra_flags.  A tuning build: nothing in the package loads it (point
     STEPPINGSTONE_LIB at it: tools/ab_libs.sh, tools/state_hash.py, tools/sched_fuzz.py)."""

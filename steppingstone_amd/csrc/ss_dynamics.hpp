@@ -287,7 +287,8 @@ SSD ABI xchg_abi(const ABI& a) {
   return o;
 }
 
-// cos/sin on the reduced range with Cody-Waite reduction; |error| ~1e-7 for the |x| < 1e3 the joints can reach.
+// cos/sin on the reduced range with Cody-Waite reduction; |error| <= 4 * 2^-24 = 2.4e-7 (absolute, against fp64 sin / cos) for the
+// |x| <= 1e3 the joints can reach: the bound tests/test_spatial_ops.py holds (measured 1.55 * 2^-24).
 // (libm's sincosf inlines a Payne-Hanek slow path per call: 21 copies of it were 3000 instructions of the kernel)
 SSD void ss_sincos(float x, float& s, float& c) {
   float k = rintf(x * 0.6366197723675814f);

@@ -1,0 +1,534 @@
+// ss_probe.hip -- calls the step kernels' spatial algebra (ss_math.hpp, ss_pair.hpp, the per-joint helpers of ss_dynamics.hpp) one
+// operator at a time, one case per lane, so that tests/test_spatial_ops.py can hold each operator against the fp64 reference of
+// tests/np_spatial.py.  TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
+//
+// The same source is compiled two ways:
+//   * for gfx950 by steppingstone_amd/build.py: build_probe() -> steppingstone_amd/lib/libss_probe.so (the product's flags); ssp_run
+//     takes DEVICE pointers and a stream, launches whole wavefronts of 64 (the lane exchange needs every lane active) and guards
+//     only its stores by n;
+//   * for the CPU by tests/probe_lib.py (-DSS_PROBE_HOST, hipcc --cuda-host-only); ssp_run loops over the cases with host pointers.
+//     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED.
+//
+//   int ssp_run(int op, int kind, int n, const float* in, float* out, void* stream)
+//     in [n][IN_W(op)], out [n][OUT_W(op)], row-major; kind 0 = ModelWalker3D, 1 = ModelMike.  Joint / body / pair numbers are
+//     columns of the input (as floats) and select the compile-time instantiation; words that are integers to the operator
+//     (Philox, xchg_u32, xchg_i) travel as raw bits.  n == 0 reads and writes nothing and returns IN_W * 1000 + OUT_W, so that the
+//     caller sizes its buffers from the library itself.  Returns 0, or a negative SSP_* / the HIP error of the launch.
+//     An op given a joint number it is not instantiated for (see the lists below) leaves zeros.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../steppingstone_amd/csrc/ss_dynamics.hpp"
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+float ss_host_xchg(float x) { return x; }      // never reached: the exchange op is refused on the host
+void ss_host_wave_sync() {}
+#endif
+
+namespace ssp {
+using namespace ss;
+
+enum {
+  OP_ROT = 0,          // [ax, c, s, v3]                           -> rot<ax> 3, rotT<ax> 3                      (float)
+  OP_ROT2,             // [ax, (c, s, v3) x 2]                     -> per half: rot 3, rotT 3                    (ssf2)
+  OP_CROSS_R,          // [J, f3]                                  -> r_J x f
+  OP_CROSS_RP,         // [i, f3 leg, f3 arm]                      -> per half 3                    joints (3+i, 13+i)
+  OP_XMOTION,          // [J, c, s, p6]                            -> 6
+  OP_XFORCE,           // [J, c, s, f6]                            -> 6
+  OP_XMOTION_P,        // [i, (c, s, p6) x 2]                      -> per half 6
+  OP_XFORCE_P,         // [i, (c, s, f6) x 2]                      -> per half 6
+  OP_XINERTIA,         // [J, c, s, abi21]                         -> abi21         abi21 = A.m[6], B[3][3] row-major, C.m[6]
+  OP_XINERTIA_P,       // [i, (c, s, abi21) x 2]                   -> per half abi21
+  OP_ABI_BODY,         // [b, abi21]                               -> abi_body<b> 21, abi_add_body<b>(input) 21
+  OP_ABI_ADD_BODYP,    // [i, abi21 x 2]                           -> per half abi21                bodies (4+i, 14+i)
+  OP_BODY_BIAS,        // [b, v6]                                  -> 6
+  OP_BODY_BIASP,       // [i, v6 x 2]                              -> per half 6                    bodies (4+i, 14+i)
+  OP_IMP_UP,           // [J, rec10, p6]                           -> 6, ul[k]      rec10 = cs, sn, Uw3, Uv3, Dinv, u
+  OP_IMP_DOWN,         // [J, loaded, rec10, ul, d6]               -> 6, dq
+  OP_IMP_DOWN_PAIR,    // [J, rec10, p6 x 2]                       -> per column 6
+  OP_IMP_UP_PAIR,      // [J, rec10, p6 x 2]                       -> per column 6, then ul2[k] (2)
+  OP_IMP_DOWN_PAIR_LD, // [J, rec10, ul2 (2), p6 x 2]              -> per column 6
+  OP_ABA_ACC,          // [J, rec10, qd, aprev6, vb6]              -> 6, qdd
+  OP_ABA_ACC_P,        // [i, (rec10, qd, aprev6, vb6) x 2]        -> per half 6, qdd
+  OP_QUAT_ROT,         // [q4]                                     -> 9
+  OP_MIRROR_SV,        // [a6]                                     -> 6
+  OP_ABI_DENSE,        // [abi21]                                  -> 36
+  OP_PACK,             // [l6, a6, abi21 l, abi21 a]               -> sv_half(sv_pack(l, a), 0 / 1), abi_half(pack, 0 / 1)
+  OP_SINCOS,           // [x]                                      -> s, c
+  OP_CHOL,             // [M 36, b0 6, b1 6]                       -> l15, di6, x(b0) 6, x(b1) 6 (float), pair solve: half 0 6, half 1 6
+  OP_XCHG,             // [f, u32, i, sv6, abi21]                  -> xchg, xchg_u32, xchg_i, xchg_sv 6, xchg_abi 21   (device only)
+  OP_PHILOX,           // [c0..c3, k0, k1, x] (raw bits)           -> out[4] (raw bits), u01(x)
+  OP_COUNT
+};
+enum { SSP_BAD_OP = -1, SSP_UNSUPPORTED = -2, SSP_BAD_KIND = -3 };
+
+constexpr int kAbi = 21, kRec = 10;
+__host__ __device__ constexpr int in_w(int op) {
+  switch (op) {
+    case OP_ROT: return 6;
+    case OP_ROT2: return 11;
+    case OP_CROSS_R: return 4;
+    case OP_CROSS_RP: return 7;
+    case OP_XMOTION: case OP_XFORCE: return 9;
+    case OP_XMOTION_P: case OP_XFORCE_P: return 17;
+    case OP_XINERTIA: return 3 + kAbi;
+    case OP_XINERTIA_P: return 1 + 2 * (2 + kAbi);
+    case OP_ABI_BODY: return 1 + kAbi;
+    case OP_ABI_ADD_BODYP: return 1 + 2 * kAbi;
+    case OP_BODY_BIAS: return 7;
+    case OP_BODY_BIASP: return 13;
+    case OP_IMP_UP: return 1 + kRec + 6;
+    case OP_IMP_DOWN: return 2 + kRec + 1 + 6;
+    case OP_IMP_DOWN_PAIR: case OP_IMP_UP_PAIR: return 1 + kRec + 12;
+    case OP_IMP_DOWN_PAIR_LD: return 1 + kRec + 2 + 12;
+    case OP_ABA_ACC: return 1 + kRec + 13;
+    case OP_ABA_ACC_P: return 1 + 2 * (kRec + 13);
+    case OP_QUAT_ROT: return 4;
+    case OP_MIRROR_SV: return 6;
+    case OP_ABI_DENSE: return kAbi;
+    case OP_PACK: return 12 + 2 * kAbi;
+    case OP_SINCOS: return 1;
+    case OP_CHOL: return 48;
+    case OP_XCHG: return 9 + kAbi;
+    case OP_PHILOX: return 7;
+    default: return 0;
+  }
+}
+__host__ __device__ constexpr int out_w(int op) {
+  switch (op) {
+    case OP_ROT: return 6;
+    case OP_ROT2: return 12;
+    case OP_CROSS_R: return 3;
+    case OP_CROSS_RP: return 6;
+    case OP_XMOTION: case OP_XFORCE: return 6;
+    case OP_XMOTION_P: case OP_XFORCE_P: return 12;
+    case OP_XINERTIA: return kAbi;
+    case OP_XINERTIA_P: return 2 * kAbi;
+    case OP_ABI_BODY: return 2 * kAbi;
+    case OP_ABI_ADD_BODYP: return 2 * kAbi;
+    case OP_BODY_BIAS: return 6;
+    case OP_BODY_BIASP: return 12;
+    case OP_IMP_UP: return 7;
+    case OP_IMP_DOWN: return 7;
+    case OP_IMP_DOWN_PAIR: return 12;
+    case OP_IMP_UP_PAIR: return 14;
+    case OP_IMP_DOWN_PAIR_LD: return 12;
+    case OP_ABA_ACC: return 7;
+    case OP_ABA_ACC_P: return 14;
+    case OP_QUAT_ROT: return 9;
+    case OP_MIRROR_SV: return 6;
+    case OP_ABI_DENSE: return 36;
+    case OP_PACK: return 12 + 2 * kAbi;
+    case OP_SINCOS: return 2;
+    case OP_CHOL: return 45;
+    case OP_XCHG: return 9 + kAbi;
+    case OP_PHILOX: return 5;
+    default: return 0;
+  }
+}
+
+// ---- rows <-> the kernels' types
+SSD SV rd_sv(const float*& p) {
+  SV a = {{p[0], p[1], p[2]}, {p[3], p[4], p[5]}};
+  p += 6;
+  return a;
+}
+SSD void wr_sv(float*& o, const SV& a) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { o[i] = a.w[i]; o[3 + i] = a.v[i]; }
+  o += 6;
+}
+SSD ABI rd_abi(const float*& p) {
+  ABI I;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { I.A.m[i] = p[i]; I.C.m[i] = p[15 + i]; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) I.B[i][j] = p[6 + 3 * i + j];
+  p += kAbi;
+  return I;
+}
+SSD void wr_abi(float*& o, const ABI& I) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { o[i] = I.A.m[i]; o[15 + i] = I.C.m[i]; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[6 + 3 * i + j] = I.B[i][j];
+  o += kAbi;
+}
+SSD JRec rd_rec(const float*& p) {
+  JRec r;
+  r.cs = p[0]; r.sn = p[1];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { r.Uw[i] = p[2 + i]; r.Uv[i] = p[5 + i]; }
+  r.Dinv = p[8]; r.u = p[9];
+  p += kRec;
+  return r;
+}
+SSD ABIP abi_pack(const ABI& l, const ABI& a) {
+  ABIP o;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { o.A.m[i] = ssf2{l.A.m[i], a.A.m[i]}; o.C.m[i] = ssf2{l.C.m[i], a.C.m[i]}; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o.B[i][j] = ssf2{l.B[i][j], a.B[i][j]};
+  return o;
+}
+SSD JRec2 rec_pack(const JRec& l, const JRec& a) {
+  JRec2 r;
+  r.cs = ssf2{l.cs, a.cs}; r.sn = ssf2{l.sn, a.sn}; r.Dinv = ssf2{l.Dinv, a.Dinv}; r.u = ssf2{l.u, a.u};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { r.Uw[i] = ssf2{l.Uw[i], a.Uw[i]}; r.Uv[i] = ssf2{l.Uv[i], a.Uv[i]}; }
+  return r;
+}
+SSD uint32_t bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+SSD float unbits(uint32_t x) { return __builtin_bit_cast(float, x); }
+
+// run f(integral_constant<J>) for the J in [LO, HI) that equals the run-time j
+template <int LO, int HI, class F>
+SSD void pick(int j, F&& f) {
+  static_for<LO, HI>([&](auto Jc) {
+    if (j == decltype(Jc)::value) f(Jc);
+  });
+}
+
+template <class Model, int OP>
+SSD void run_case(const float* p, float* o) {
+  if constexpr (OP == OP_ROT) {
+    const int ax = (int)p[0];
+    const float c = p[1], s = p[2], v[3] = {p[3], p[4], p[5]};
+    pick<0, 3>(ax, [&](auto Ac) {
+      constexpr int AX = decltype(Ac)::value;
+      rot<AX>(c, s, v, o);
+      rotT<AX>(c, s, v, o + 3);
+    });
+  } else if constexpr (OP == OP_ROT2) {
+    const int ax = (int)p[0];
+    const ssf2 c = {p[1], p[6]}, s = {p[2], p[7]}, v[3] = {{p[3], p[8]}, {p[4], p[9]}, {p[5], p[10]}};
+    pick<0, 3>(ax, [&](auto Ac) {
+      constexpr int AX = decltype(Ac)::value;
+      ssf2 a[3], b[3];
+      rot<AX>(c, s, v, a);
+      rotT<AX>(c, s, v, b);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { o[i] = a[i].x; o[3 + i] = b[i].x; o[6 + i] = a[i].y; o[9 + i] = b[i].y; }
+    });
+  } else if constexpr (OP == OP_CROSS_R) {
+    const float f[3] = {p[1], p[2], p[3]};
+    pick<0, NJ>((int)p[0], [&](auto Jc) { cross_r<Model, decltype(Jc)::value>(f, o); });
+  } else if constexpr (OP == OP_CROSS_RP) {
+    const ssf2 f[3] = {{p[1], p[4]}, {p[2], p[5]}, {p[3], p[6]}};
+    pick<0, 4>((int)p[0], [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      ssf2 t[3];
+      cross_rP<Model, 3 + i, 13 + i>(f, t);
+#pragma unroll
+      for (int m = 0; m < 3; ++m) { o[m] = t[m].x; o[3 + m] = t[m].y; }
+    });
+  } else if constexpr (OP == OP_XMOTION || OP == OP_XFORCE) {
+    const int j = (int)p[0];
+    const float c = p[1], s = p[2];
+    p += 3;
+    const SV a = rd_sv(p);
+    pick<0, NJ>(j, [&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      if constexpr (OP == OP_XMOTION) wr_sv(o, xmotion<Model, J>(c, s, a));
+      else wr_sv(o, xforce<Model, J>(c, s, a));
+    });
+  } else if constexpr (OP == OP_XMOTION_P || OP == OP_XFORCE_P) {
+    const int i_ = (int)p[0];
+    const ssf2 c = {p[1], p[9]}, s = {p[2], p[10]};
+    const float *pl = p + 3, *pa = p + 11;
+    const SV2 a = sv_pack(rd_sv(pl), rd_sv(pa));
+    pick<0, 4>(i_, [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      using JT = PairJoint<Model, 3 + i, 13 + i>;
+      SV2 r;
+      if constexpr (OP == OP_XMOTION_P) r = xmotion<JT>(c, s, a);
+      else r = xforce<JT>(c, s, a);
+      wr_sv(o, sv_half(r, 0));
+      wr_sv(o, sv_half(r, 1));
+    });
+  } else if constexpr (OP == OP_XINERTIA) {
+    const int j = (int)p[0];
+    const float c = p[1], s = p[2];
+    p += 3;
+    const ABI I = rd_abi(p);
+    pick<0, NJ>(j, [&](auto Jc) { wr_abi(o, xinertia<Model, decltype(Jc)::value>(c, s, I)); });
+  } else if constexpr (OP == OP_XINERTIA_P) {
+    const int i_ = (int)p[0];
+    const ssf2 c = {p[1], p[3 + kAbi]}, s = {p[2], p[4 + kAbi]};
+    const float *pl = p + 3, *pa = p + 5 + kAbi;
+    const ABIP I = abi_pack(rd_abi(pl), rd_abi(pa));
+    pick<0, 4>(i_, [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      const ABIP r = xinertia<PairJoint<Model, 3 + i, 13 + i>>(c, s, I);
+      wr_abi(o, abi_half(r, 0));
+      wr_abi(o, abi_half(r, 1));
+    });
+  } else if constexpr (OP == OP_ABI_BODY) {
+    const int b = (int)p[0];
+    p += 1;
+    ABI I = rd_abi(p);
+    pick<0, NB>(b, [&](auto Bc) {
+      constexpr int Bd = decltype(Bc)::value;
+      wr_abi(o, abi_body<Model, Bd>());
+      abi_add_body<Model, Bd>(I);
+      wr_abi(o, I);
+    });
+  } else if constexpr (OP == OP_ABI_ADD_BODYP) {
+    const int i_ = (int)p[0];
+    p += 1;
+    const ABI Il = rd_abi(p), Ia = rd_abi(p);
+    ABIP I = abi_pack(Il, Ia);
+    pick<0, 4>(i_, [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      abi_add_bodyP<Model, 4 + i, 14 + i>(I);
+      wr_abi(o, abi_half(I, 0));
+      wr_abi(o, abi_half(I, 1));
+    });
+  } else if constexpr (OP == OP_BODY_BIAS) {
+    const int b = (int)p[0];
+    p += 1;
+    const SV v = rd_sv(p);
+    pick<0, NB>(b, [&](auto Bc) { wr_sv(o, body_bias<Model, decltype(Bc)::value>(v)); });
+  } else if constexpr (OP == OP_BODY_BIASP) {
+    const int i_ = (int)p[0];
+    p += 1;
+    const SV vl = rd_sv(p), va = rd_sv(p);
+    const SV2 v = sv_pack(vl, va);
+    pick<0, 4>(i_, [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      const SV2 r = body_biasP<Model, 4 + i, 14 + i>(v);
+      wr_sv(o, sv_half(r, 0));
+      wr_sv(o, sv_half(r, 1));
+    });
+  } else if constexpr (OP == OP_IMP_UP) {
+    // ss_dynamics.hpp, solve(): "accumulated foot wrenches -> whole tree": imp_up<Model, 7..3> then <2..0>
+    const int j = (int)p[0];
+    p += 1;
+    const JRec r = rd_rec(p);
+    const SV a = rd_sv(p);
+    pick<0, 8>(j, [&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      JointCache jc;
+      jc.r[half_pos(J)] = r;
+      float ul[NH];
+      wr_sv(o, imp_up<Model, J>(jc, ul, a));
+      o[0] = ul[half_pos(J)];
+    });
+  } else if constexpr (OP == OP_IMP_DOWN) {
+    // same place: imp_down<Model, 0..7, true> down spine and leg, imp_down<Model, 13..16, false> down the arm
+    const int j = (int)p[0];
+    const bool loaded = p[1] != 0.f;
+    p += 2;
+    const JRec r = rd_rec(p);
+    const float ulk = p[0];
+    p += 1;
+    const SV a = rd_sv(p);
+    pick<0, 17>(j, [&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      if constexpr (J <= 7 || J >= 13) {
+        JointCache jc;
+        jc.r[half_pos(J)] = r;
+        float ul[NH];
+        ul[half_pos(J)] = ulk;
+        float dq = 0.f;
+        if constexpr (J <= 7) {
+          if (loaded) wr_sv(o, imp_down<Model, J, true>(jc, ul, a, &dq));
+        } else {
+          if (!loaded) wr_sv(o, imp_down<Model, J, false>(jc, ul, a, &dq));
+        }
+        if ((J <= 7) == loaded) o[0] = dq;
+      }
+    });
+  } else if constexpr (OP == OP_IMP_DOWN_PAIR || OP == OP_IMP_UP_PAIR || OP == OP_IMP_DOWN_PAIR_LD) {
+    // imp_down_pair<Model, 3..7>: operator_T; <0..7> through imp_down_pair_loaded.  imp_up_pair<Model, 7..3>: operator_up, <2..0>:
+    // operator_pair_b.  imp_down_pair_loaded<Model, 0..2> and <3..7>: operator_pair_b.  The pair is two COLUMNS through one joint.
+    const int j = (int)p[0];
+    p += 1;
+    const JRec r = rd_rec(p);
+    ssf2 ulk = {0.f, 0.f};
+    if constexpr (OP == OP_IMP_DOWN_PAIR_LD) { ulk = ssf2{p[0], p[1]}; p += 2; }
+    const SV a0 = rd_sv(p), a1 = rd_sv(p);
+    const SV2 a = sv_pack(a0, a1);
+    pick<0, 8>(j, [&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      JointCache jc;
+      jc.r[half_pos(J)] = r;
+      ssf2 ul2[NH];
+      ul2[half_pos(J)] = ulk;
+      SV2 d;
+      if constexpr (OP == OP_IMP_DOWN_PAIR) d = imp_down_pair<Model, J>(jc, a);
+      else if constexpr (OP == OP_IMP_UP_PAIR) d = imp_up_pair<Model, J>(jc, ul2, a);
+      else d = imp_down_pair_loaded<Model, J>(jc, ul2, a);
+      wr_sv(o, sv_half(d, 0));
+      wr_sv(o, sv_half(d, 1));
+      if constexpr (OP == OP_IMP_UP_PAIR) { o[0] = ul2[half_pos(J)].x; o[1] = ul2[half_pos(J)].y; }
+    });
+  } else if constexpr (OP == OP_ABA_ACC) {
+    // substep(), pass 3, acc_scalar: aba_acc<Joint<Model, j>> for the spine 0, 1, 2 and the ankle 7
+    const int j = (int)p[0];
+    p += 1;
+    const JRec r = rd_rec(p);
+    const float qd = p[0];
+    p += 1;
+    const SV ap = rd_sv(p), vb = rd_sv(p);
+    pick<0, 8>(j, [&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      if constexpr (J <= 2 || J == 7) {
+        float qdd;
+        wr_sv(o, aba_acc<Joint<Model, J>>(r, qd, ap, vb, qdd));
+        o[0] = qdd;
+      }
+    });
+  } else if constexpr (OP == OP_ABA_ACC_P) {
+    // substep(), pass 3: aba_acc<PairJoint<Model, 3 + i, 13 + i>> for i = 0..3
+    const int i_ = (int)p[0];
+    p += 1;
+    const JRec rl = rd_rec(p);
+    const float qdl = p[0];
+    p += 1;
+    const SV apl = rd_sv(p), vbl = rd_sv(p);
+    const JRec ra = rd_rec(p);
+    const float qda = p[0];
+    p += 1;
+    const SV apa = rd_sv(p), vba = rd_sv(p);
+    const JRec2 r = rec_pack(rl, ra);
+    const ssf2 qd = {qdl, qda};
+    const SV2 ap = sv_pack(apl, apa), vb = sv_pack(vbl, vba);
+    pick<0, 4>(i_, [&](auto Ic) {
+      constexpr int i = decltype(Ic)::value;
+      ssf2 qdd;
+      const SV2 a = aba_acc<PairJoint<Model, 3 + i, 13 + i>>(r, qd, ap, vb, qdd);
+      wr_sv(o, sv_half(a, 0));
+      o[0] = qdd.x;
+      o += 1;
+      wr_sv(o, sv_half(a, 1));
+      o[0] = qdd.y;
+    });
+  } else if constexpr (OP == OP_QUAT_ROT) {
+    const float q[4] = {p[0], p[1], p[2], p[3]};
+    float R[3][3];
+    quat_rot(q, R);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) o[3 * i + j] = R[i][j];
+  } else if constexpr (OP == OP_MIRROR_SV) {
+    wr_sv(o, mirror_sv(rd_sv(p)));
+  } else if constexpr (OP == OP_ABI_DENSE) {
+    const ABI I = rd_abi(p);
+    float M[6][6];
+    abi_dense(I, M);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) o[6 * i + j] = M[i][j];
+  } else if constexpr (OP == OP_PACK) {
+    const SV l = rd_sv(p), a = rd_sv(p);
+    const ABI Il = rd_abi(p), Ia = rd_abi(p);
+    const SV2 s2 = sv_pack(l, a);
+    const ABIP I2 = abi_pack(Il, Ia);
+    wr_sv(o, sv_half(s2, 0));
+    wr_sv(o, sv_half(s2, 1));
+    wr_abi(o, abi_half(I2, 0));
+    wr_abi(o, abi_half(I2, 1));
+  } else if constexpr (OP == OP_SINCOS) {
+    ss_sincos(p[0], o[0], o[1]);
+  } else if constexpr (OP == OP_CHOL) {
+    float M[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) M[i][j] = p[6 * i + j];
+    p += 36;
+    const SV b0 = rd_sv(p), b1 = rd_sv(p);
+    const Chol6 L = chol6(M);
+#pragma unroll
+    for (int i = 0; i < 15; ++i) o[i] = L.l[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) o[15 + i] = L.di[i];
+    o += 21;
+    wr_sv(o, chol6_solve_neg(L, b0));
+    wr_sv(o, chol6_solve_neg(L, b1));
+    const SV2 x2 = chol6_solve_neg(L, sv_pack(b0, b1));
+    wr_sv(o, sv_half(x2, 0));
+    wr_sv(o, sv_half(x2, 1));
+  } else if constexpr (OP == OP_XCHG) {
+    o[0] = xchg(p[0]);
+    o[1] = unbits(xchg_u32(bits(p[1])));
+    o[2] = unbits((uint32_t)xchg_i((int)bits(p[2])));
+    p += 3;
+    o += 3;
+    const SV a = rd_sv(p);
+    const ABI I = rd_abi(p);
+    wr_sv(o, xchg_sv(a));
+    wr_abi(o, xchg_abi(I));
+  } else if constexpr (OP == OP_PHILOX) {
+    uint32_t r[4];
+    philox4x32_10(bits(p[0]), bits(p[1]), bits(p[2]), bits(p[3]), bits(p[4]), bits(p[5]), r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = unbits(r[i]);
+    o[4] = u01(bits(p[6]));
+  }
+}
+
+#if !defined(SS_PROBE_HOST)
+// one wavefront per workgroup, one case per lane.  Lanes past n redo case n - 1 (every lane stays active and reads inside the
+// buffer); only lanes below n store.
+template <class Model, int OP>
+__global__ __launch_bounds__(kWave) void probe_kernel(int n, const float* __restrict__ in, float* __restrict__ out) {
+  constexpr int IW = in_w(OP), OW = out_w(OP);
+  const int idx = blockIdx.x * kWave + threadIdx.x;
+  const int src = idx < n ? idx : n - 1;
+  float row[IW], o[OW];
+#pragma unroll
+  for (int i = 0; i < IW; ++i) row[i] = in[(size_t)src * IW + i];
+#pragma unroll
+  for (int i = 0; i < OW; ++i) o[i] = 0.f;
+  run_case<Model, OP>(row, o);
+  if (idx < n) {
+#pragma unroll
+    for (int i = 0; i < OW; ++i) out[(size_t)idx * OW + i] = o[i];
+  }
+}
+#endif
+
+template <class Model>
+int run(int op, int n, const float* in, float* out, void* stream) {
+  int rc = SSP_BAD_OP;
+  static_for<0, OP_COUNT>([&](auto Oc) {
+    constexpr int OP = decltype(Oc)::value;
+    if (op != OP) return;
+    if (n == 0) { rc = in_w(OP) * 1000 + out_w(OP); return; }
+#if defined(SS_PROBE_HOST)
+    (void)stream;
+    if (OP == OP_XCHG) { rc = SSP_UNSUPPORTED; return; }
+    for (int e = 0; e < n; ++e) {
+      float o[out_w(OP)];
+      for (int i = 0; i < out_w(OP); ++i) o[i] = 0.f;
+      run_case<Model, OP>(in + (size_t)e * in_w(OP), o);
+      for (int i = 0; i < out_w(OP); ++i) out[(size_t)e * out_w(OP) + i] = o[i];
+    }
+    rc = 0;
+#else
+    (void)hipGetLastError();      // what this call returns speaks of this launch alone
+    probe_kernel<Model, OP><<<dim3((n + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream>>>(n, in, out);
+    rc = -(int)hipGetLastError();
+#endif
+  });
+  return rc;
+}
+}  // namespace ssp
+
+extern "C" int ssp_run(int op, int kind, int n, const float* in, float* out, void* stream) {
+  if (n < 0 || (n > 0 && (!in || !out))) return ssp::SSP_BAD_OP;
+  if (kind == 0) return ssp::run<ss::ModelWalker3D>(op, n, in, out, stream);
+  if (kind == 1) return ssp::run<ss::ModelMike>(op, n, in, out, stream);
+  return ssp::SSP_BAD_KIND;
+}
