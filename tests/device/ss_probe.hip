@@ -1,6 +1,8 @@
 // ss_probe.hip -- calls the step kernels' spatial algebra (ss_math.hpp, ss_pair.hpp, the per-joint helpers of ss_dynamics.hpp) one
 // operator at a time, one case per lane, so that tests/test_spatial_ops.py can hold each operator against the fp64 reference of
-// tests/np_spatial.py.  TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
+// tests/np_spatial.py; and, the same way, the contact stage of ss_dynamics.hpp (detection, Jacobian rows, contact-space operators) and
+// the env formulas of ss_kernels.hpp (sampler, observation terms, reset noise) for tests/test_contact_ops.py / tests/np_contact_ops.py.
+// TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
 //
 // The same source is compiled two ways:
 //   * for gfx950 by steppingstone_amd/build.py: build_probe() -> steppingstone_amd/lib/libss_probe.so (the product's flags); ssp_run
@@ -15,14 +17,19 @@
 //     (Philox, xchg_u32, xchg_i) travel as raw bits.  n == 0 reads and writes nothing and returns IN_W * 1000 + OUT_W, so that the
 //     caller sizes its buffers from the library itself.  Returns 0, or a negative SSP_* / the HIP error of the launch.
 //     An op given a joint number it is not instantiated for (see the lists below) leaves zeros.
+//   The ops from fk_detect on work on a lane-private Lds view as the step kernels do: on the device one __shared__ block of
+//   kLdsSlots * kWave float4 per wavefront and Lds{base, lane}; on the host one such block per case (filled with NaN first) and lane 0.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "../../steppingstone_amd/csrc/ss_dynamics.hpp"
+#include <limits>
+#include <vector>
+
+#include "../../steppingstone_amd/csrc/ss_kernels.hpp"
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-float ss_host_xchg(float x) { return x; }      // never reached: the exchange op is refused on the host
+float ss_host_xchg(float x) { return x; }      // the identity: contact_ops forms C with the lane as its own partner (the exchange op itself is refused)
 void ss_host_wave_sync() {}
 #endif
 
@@ -59,6 +66,23 @@ enum {
   OP_CHOL,             // [M 36, b0 6, b1 6]                       -> l15, di6, x(b0) 6, x(b1) 6 (float), pair solve: half 0 6, half 1 6
   OP_XCHG,             // [f, u32, i, sv6, abi21]                  -> xchg, xchg_u32, xchg_i, xchg_sv 6, xchg_abi 21   (device only)
   OP_PHILOX,           // [c0..c3, k0, k1, x] (raw bits)           -> out[4] (raw bits), u01(x)
+  // ---- the contact stage and the env formulas.  Integers travel as float VALUES here (all are small).  A 6x6 operator is six columns of
+  // six (column-major; a column is w0 w1 w2 v0 v1 v2).
+  OP_FK_DETECT,        // [cs8, sn8, Rb 9 (row-major), pos 3, (centre 3, normal 3, cos, sin of the heading) x stones n-1, n, n+1]
+                       //                                          -> per coding (BRANCHFREE, then &&): Rf 9, pen 4, active, cslot, contact, on_target, sole 3
+  OP_JACOBIAN_ROWS,    // [Rf 9, pen 4, active, cslot, normal 3 x 3 stones] -> rWp: 12 rows (corner * 3 + direction) of (c x dir 3, dir 3), rB 4
+  OP_CONTACT_OPS,      // [rec10 x 8 (joints 0..7), l15, di6]      -> T 36, C 36, Lambda_own 36 (T, C read back from kLdsT / kLdsC), then the
+                       //                                             intermediates of operator_pair_b, formed a second time from the same calls:
+                       //                                             p 36 (the impulses at the base), x 36 (the base solve), G 36 (pelvis twist);
+                       //                                             device: lanes 2i, 2i + 1 are the two feet of a robot; host: the lane is its own partner
+  OP_SAMPLER,          // [prob 121, u, (px, py, pz, dr, cp, sp, cph, sph), (phi, xt, yt)]
+                       //                                          -> sample_cell: shared grid, per-env grid [121][kWave]; yaw_sample(0..10), pitch_sample(0..10),
+                       //                                             place_stone 3, stone_normal 3
+  OP_WINDOW_PROB,      // [level, ring]                            -> 121                                       (host only)
+  OP_OBS_TERMS,        // [quat 4, (cy, sy), pos 3, stone 3, tilt 2, x, q 21, qd 21, 6 Philox blocks (24 words, raw bits)]
+                       //                                          -> roll, pitch, cy, sy (quat); target_features 5 (given cy, sy); planar_dist(stone, pos);
+                       //                                             clip5(x); obs_angle 21; obs_rate 21; reset_angle 21; reset_angle 21 over
+                       //                                             ClampModel (below), whose draws reach the clamps
   OP_COUNT
 };
 enum { SSP_BAD_OP = -1, SSP_UNSUPPORTED = -2, SSP_BAD_KIND = -3 };
@@ -92,9 +116,16 @@ __host__ __device__ constexpr int in_w(int op) {
     case OP_CHOL: return 48;
     case OP_XCHG: return 9 + kAbi;
     case OP_PHILOX: return 7;
+    case OP_FK_DETECT: return 16 + 9 + 3 + 24;
+    case OP_JACOBIAN_ROWS: return 9 + 4 + 2 + 9;
+    case OP_CONTACT_OPS: return 8 * kRec + 21;
+    case OP_SAMPLER: return SS_NCELL + 1 + 8 + 3;
+    case OP_WINDOW_PROB: return 2;
+    case OP_OBS_TERMS: return 15 + 2 * NJ + 24;
     default: return 0;
   }
 }
+__host__ __device__ constexpr bool needs_lds(int op) { return op >= OP_FK_DETECT; }
 __host__ __device__ constexpr int out_w(int op) {
   switch (op) {
     case OP_ROT: return 6;
@@ -124,6 +155,12 @@ __host__ __device__ constexpr int out_w(int op) {
     case OP_CHOL: return 45;
     case OP_XCHG: return 9 + kAbi;
     case OP_PHILOX: return 5;
+    case OP_FK_DETECT: return 2 * 20;
+    case OP_JACOBIAN_ROWS: return 72 + 4;
+    case OP_CONTACT_OPS: return 216;
+    case OP_SAMPLER: return 2 + 22 + 3 + 3;
+    case OP_WINDOW_PROB: return SS_NCELL;
+    case OP_OBS_TERMS: return 11 + 4 * NJ;
     default: return 0;
   }
 }
@@ -196,8 +233,36 @@ SSD void pick(int j, F&& f) {
   });
 }
 
+// every lane of the wavefront has finished with the shared block (the sampler stages two layouts in it, one after the other)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SSP_WAVE_SYNC() __syncthreads()
+#else
+#define SSP_WAVE_SYNC() ((void)0)
+#endif
+SSD void wr_col(float* o, int col, const ssf2& a, const ssf2& b, const ssf2& c) {
+  o[6 * col + 0] = a.x; o[6 * col + 1] = a.y; o[6 * col + 2] = b.x; o[6 * col + 3] = b.y; o[6 * col + 4] = c.x; o[6 * col + 5] = c.y;
+}
+
+// the two columns a packed recursion carries, as columns 2c and 2c + 1 of a column-major 6x6
+SSD void wr_pair(float* dst, const SV2& a) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { dst[i] = a.w[i].x; dst[3 + i] = a.v[i].x; dst[6 + i] = a.w[i].y; dst[9 + i] = a.v[i].y; }
+}
+// reset_angle's clamps cannot be reached with the shipped robots (no q0 within 0.07 of a limit).  This model exists for that one
+// function: q0 sits 0.03 inside lo (even joints) or hi (odd joints) of ranges of different sizes, so the draws q0 +- 0.05 meet
+// lo + 0.02 / hi - 0.02 from both sides.
+struct ClampModel {
+  static constexpr float lo[21] = {-1.0f, -0.5f, -0.25f, 0.1f, -2.0f, -0.3f, 0.7f, -1.5f, -0.6f, 0.2f, -0.9f,
+                                   -1.1f, -0.4f, 0.3f, -2.5f, -0.7f, 0.5f, -1.3f, -0.8f, 0.4f, -0.2f};
+  static constexpr float hi[21] = {1.0f, 0.75f, 0.5f, 1.1f, -0.5f, 0.3f, 2.9f, 0.6f, 0.6f, 1.2f, 0.9f,
+                                   1.3f, 0.4f, 2.3f, -1.5f, 0.7f, 1.5f, -0.3f, 0.8f, 0.9f, 0.2f};
+  static constexpr float q0[21] = {-0.97f, 0.72f, -0.22f, 1.07f, -1.97f, 0.27f, 0.73f, 0.57f, -0.57f, 1.17f, -0.87f,
+                                   1.27f, -0.37f, 2.27f, -2.47f, 0.67f, 0.53f, -0.33f, -0.77f, 0.87f, -0.17f};
+};
+
 template <class Model, int OP>
-SSD void run_case(const float* p, float* o) {
+SSD void run_case(const float* p, float* o, const Lds& L) {
+  (void)L;
   if constexpr (OP == OP_ROT) {
     const int ax = (int)p[0];
     const float c = p[1], s = p[2], v[3] = {p[3], p[4], p[5]};
@@ -475,6 +540,137 @@ SSD void run_case(const float* p, float* o) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = unbits(r[i]);
     o[4] = u01(bits(p[6]));
+  } else if constexpr (OP == OP_FK_DETECT) {
+    // the stones as the step kernel places them: S_POS, S_STP, S_STN (scalars) and the headings as float2 items at kLdsHead
+    float Rb[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Rb[i][j] = p[16 + 3 * i + j];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) L.s(S_POS + a) = p[25 + a];
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { L.s(S_STP + sl * 3 + i) = p[28 + sl * 8 + i]; L.s(S_STN + sl * 3 + i) = p[28 + sl * 8 + 3 + i]; }
+      L.q2(kLdsHead + sl) = make_float2(p[28 + sl * 8 + 6], p[28 + sl * 8 + 7]);
+    }
+    static_for<0, 2>([&](auto Bc) {
+      constexpr bool BRANCHFREE = decltype(Bc)::value == 0;
+      DetectOut det;
+      FootReport fr;
+      fk_detect<Model, BRANCHFREE>(p, p + 8, Rb, L, det, fr);
+      float* q = o + 20 * decltype(Bc)::value;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q[3 * i + j] = det.Rf[i][j];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[9 + k] = det.pen[k];
+      q[13] = (float)det.active; q[14] = (float)det.cslot; q[15] = (float)fr.contact; q[16] = (float)fr.on_target;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) q[17 + i] = fr.sole[i];
+    });
+  } else if constexpr (OP == OP_JACOBIAN_ROWS) {
+    DetectOut det;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) det.Rf[i][j] = p[3 * i + j];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) det.pen[k] = p[9 + k];
+    det.active = (int)p[13];
+    det.cslot = (int)p[14];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) L.s(S_STN + i) = p[15 + i];
+    ssf2 rWp[12][3];
+    float rB[4];
+    jacobian_rows<Model>(det, L, rWp, rB);
+#pragma unroll
+    for (int row = 0; row < 12; ++row) wr_col(o, row, rWp[row][0], rWp[row][1], rWp[row][2]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[72 + k] = rB[k];
+  } else if constexpr (OP == OP_CONTACT_OPS) {
+    // substep(), the HELPERS == 0 branch: opaque copies of the records, all six T columns, then per column pair up the leg and part B
+    JointCache jin, jo;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) jin.r[k] = rd_rec(p);
+#pragma unroll
+    for (int i = 0; i < 15; ++i) jin.L0.l[i] = p[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) jin.L0.di[i] = p[15 + i];
+    operator_records_leg(jin, jo);
+    operator_records_spine(jin, jo);
+    static_for<0, 3>([&](auto Cc) { operator_T<Model, decltype(Cc)::value>(jo, L); });
+    static_for<0, 3>([&](auto Cc) {
+      constexpr int c = decltype(Cc)::value;
+      OpCarry oc;
+      operator_up<Model, c>(jo, oc);
+      const LamPair lp = operator_pair_b<Model, c>(L, jo, oc);
+      wr_col(o + 72, 2 * c, lp.a[0], lp.a[1], lp.a[2]);
+      wr_col(o + 72, 2 * c + 1, lp.b[0], lp.b[1], lp.b[2]);
+      // the first half of operator_pair_b once more, for its intermediates (the same calls on the same data: the same bits)
+      OpCarry o2;
+      operator_up<Model, c>(jo, o2);
+      SV2 pp = o2.p;
+      static_rfor<2, 0>([&](auto Jc) { pp = imp_up_pair<Model, decltype(Jc)::value>(jo, o2.ul2, pp); });
+      SV2 dd = chol6_solve_neg(jo.L0, pp);
+      const SV2 xx = dd;
+      static_for<0, 3>([&](auto Jc) { dd = imp_down_pair_loaded<Model, decltype(Jc)::value>(jo, o2.ul2, dd); });
+      wr_pair(o + 108 + 12 * c, pp);
+      wr_pair(o + 144 + 12 * c, xx);
+      wr_pair(o + 180 + 12 * c, dd);
+    });
+#pragma unroll
+    for (int l = 0; l < 6; ++l)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float2 t = L.q2(kLdsT + l * 3 + i), c = L.q2(kLdsC + l * 3 + i);
+        o[6 * l + 2 * i] = t.x; o[6 * l + 2 * i + 1] = t.y;
+        o[36 + 6 * l + 2 * i] = c.x; o[36 + 6 * l + 2 * i + 1] = c.y;
+      }
+  } else if constexpr (OP == OP_SAMPLER) {
+    Params P = {};
+    Knobs K = {};
+    P.npad = kWave;
+    const float u = p[SS_NCELL];
+    float* shared_grid = L.base + L.lane * SS_NCELL;        // a [121] grid of this lane's own
+    for (int k = 0; k < SS_NCELL; ++k) shared_grid[k] = p[k];
+    K.prob = shared_grid; K.per_env_prob = 0;
+    o[0] = (float)sample_cell(P, K, L.lane, u);
+    SSP_WAVE_SYNC();
+    for (int k = 0; k < SS_NCELL; ++k) L.base[k * kWave + L.lane] = p[k];      // [121][npad], npad = kWave: env = lane
+    K.prob = L.base; K.per_env_prob = 1;
+    o[1] = (float)sample_cell(P, K, L.lane, u);
+#pragma unroll
+    for (int i = 0; i < SS_GRID; ++i) { o[2 + i] = yaw_sample(i); o[2 + SS_GRID + i] = pitch_sample(i); }
+    const float* s = p + SS_NCELL + 1;
+    place_stone(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], o + 24);
+    stone_normal(s[8], s[9], s[10], o + 27);
+  } else if constexpr (OP == OP_WINDOW_PROB) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    window_prob(o, (int)p[0], p[1] != 0.f);
+#endif
+  } else if constexpr (OP == OP_OBS_TERMS) {
+    quat_roll_pitch_cs(p, o[0], o[1], o[2], o[3]);
+    target_features(p + 6, p[4], p[5], p + 9, p + 12, o + 4);
+    o[9] = planar_dist(p + 9, p + 6);
+    o[10] = clip5(p[14]);
+    uint32_t r[6][4];
+#pragma unroll
+    for (int b = 0; b < 6; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[b][i] = bits(p[15 + 2 * NJ + 4 * b + i]);
+    static_for<0, NJ>([&](auto Jc) {      // instantiated as write_obs / env_reset do
+      constexpr int j = decltype(Jc)::value;
+      constexpr float mid = 0.5f * (Model::lo[j] + Model::hi[j]);
+      constexpr float span = Model::hi[j] - Model::lo[j];
+      constexpr float ps = (float)kPolicySign[j];
+      o[11 + j] = obs_angle(ps, p[15 + j], mid, span);
+      o[11 + NJ + j] = obs_rate(ps, p[15 + NJ + j]);
+      o[11 + 2 * NJ + j] = reset_angle<Model, j>(r);
+      o[11 + 3 * NJ + j] = reset_angle<ClampModel, j>(r);
+    });
   }
 }
 
@@ -491,7 +687,12 @@ __global__ __launch_bounds__(kWave) void probe_kernel(int n, const float* __rest
   for (int i = 0; i < IW; ++i) row[i] = in[(size_t)src * IW + i];
 #pragma unroll
   for (int i = 0; i < OW; ++i) o[i] = 0.f;
-  run_case<Model, OP>(row, o);
+  Lds L = {nullptr, (int)threadIdx.x};
+  if constexpr (needs_lds(OP)) {
+    __shared__ float4 lds[kLdsSlots * kWave];
+    L.base = reinterpret_cast<float*>(lds);
+  }
+  run_case<Model, OP>(row, o, L);
   if (idx < n) {
 #pragma unroll
     for (int i = 0; i < OW; ++i) out[(size_t)idx * OW + i] = o[i];
@@ -509,17 +710,24 @@ int run(int op, int n, const float* in, float* out, void* stream) {
 #if defined(SS_PROBE_HOST)
     (void)stream;
     if (OP == OP_XCHG) { rc = SSP_UNSUPPORTED; return; }
+    std::vector<float> lds(needs_lds(OP) ? (size_t)kLdsSlots * kWave * 4 : 0);
+    const Lds L = {lds.data(), 0};
     for (int e = 0; e < n; ++e) {
       float o[out_w(OP)];
       for (int i = 0; i < out_w(OP); ++i) o[i] = 0.f;
-      run_case<Model, OP>(in + (size_t)e * in_w(OP), o);
+      for (float& x : lds) x = std::numeric_limits<float>::quiet_NaN();
+      run_case<Model, OP>(in + (size_t)e * in_w(OP), o, L);
       for (int i = 0; i < out_w(OP); ++i) out[(size_t)e * out_w(OP) + i] = o[i];
     }
     rc = 0;
 #else
-    (void)hipGetLastError();      // what this call returns speaks of this launch alone
-    probe_kernel<Model, OP><<<dim3((n + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream>>>(n, in, out);
-    rc = -(int)hipGetLastError();
+    if constexpr (OP == OP_WINDOW_PROB) {      // host code of the product: there is nothing to launch
+      rc = SSP_UNSUPPORTED;
+    } else {
+      (void)hipGetLastError();      // what this call returns speaks of this launch alone
+      probe_kernel<Model, OP><<<dim3((n + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream>>>(n, in, out);
+      rc = -(int)hipGetLastError();
+    }
 #endif
   });
   return rc;
