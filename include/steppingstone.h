@@ -38,7 +38,8 @@ extern "C" {
                             * MEANING, no layout: actions and observations carry POLICY coordinates, see "Joint conventions".
                             * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) and the per-env
                             * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
-                            * existing layout or meaning changed, so a version-4 binding keeps working. */
+                            * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
+                            * readout (ss_kinematics). */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -224,6 +225,26 @@ int ss_body_poses(ss_env* env, float* out, void* stream);
  * nothing.  An env id outside [0, N) lives on the device and is not checked here: that env is drawn as background. */
 int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int32_t height, const ss_camera* cam, uint8_t* rgb,
               float* depth, uint8_t* seg, void* stream);
+
+/* Whole-body kinematic readout of the m envs listed in env_ids (docs/PHYSICS.md "Kinematic readout" has the definitions); added under
+ * version 4 (nothing existing moved).  It only READS the environment state, is ordered on `stream`, never synchronises the host and
+ * allocates nothing.  env_ids: DEVICE [m] int32 as in ss_get_state_envs, row k of every output describes env env_ids[k]; env_ids ==
+ * NULL means envs 0..m-1 and needs m == N.  m == 0 does nothing.  An id outside [0, N) lives on the device and is not checked here: no
+ * row of it is read or written.  Outputs are DEVICE pointers, 16-byte aligned, f32; any may be NULL, not all three when m > 0.  Bad host
+ * arguments return SS_ERR_INVALID and launch nothing.  A row's bits depend on the env's state alone: not on N, m, k or the outputs asked for.
+ *   body_twist [m,22,6]: world-frame twist of body b (the bodies and link frames of ss_body_poses; massless intermediate links
+ *     included): 0:3 angular velocity, 3:6 linear velocity of the origin of the link frame.
+ *   summary [m,SS_KIN_SUMMARY]: 0:3 centre of mass | 3:6 its velocity (total linear momentum / total mass) | 6:9 angular momentum about
+ *     the centre of mass | 9 kinetic energy of the rigid bodies, sum_b (m_b |v_c,b|^2 + w_b . I_c,b w_b) / 2 -- the rotor ARMATURE of
+ *     the joints (PHYSICS.md 3.1) is NOT included | 10 potential energy M * 9.8 * com_z | 11 total mass M.
+ *   corners [m,SS_KIN_CORNER,8]: sole corner c = 4 * foot + corner (foot 0 = right, 1 = left; corner order of the model's `corners`,
+ *     PHYSICS.md 2): 0:3 world position | 3:6 world velocity | 6 signed height h = (x - s_n) . n_n over the surface plane of the
+ *     target stone n (negative below the surface; the contact set is -0.10 < h < 0) | 7 carrier, as a float: 0, 1 or 2 when the stone
+ *     in slot n-1, n or n+1 carries the corner (PHYSICS.md 3.3: the decision of the step kernels' own detection code, tie rule
+ *     included), -1 when none does. */
+#define SS_KIN_SUMMARY 12
+#define SS_KIN_CORNER 8
+int ss_kinematics(ss_env* env, const int32_t* env_ids, int32_t m, float* body_twist, float* summary, float* corners, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

@@ -18,6 +18,9 @@ namespace ss {
 hipError_t launch_render(const Params& P, int kind, const int32_t* env_ids, int m, int W, int H, const ss_camera& cam,
                          unsigned char* rgb, float* depth, unsigned char* seg, hipStream_t st);
 hipError_t launch_body_poses(const Params& P, int kind, float* out, hipStream_t st);
+// compiled in ss_kinematics.hip (the kinematic readout, docs/PHYSICS.md)
+hipError_t launch_kinematics(const Params& P, int kind, const int32_t* env_ids, int m, float* body_twist, float* summary, float* corners,
+                             hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -759,6 +762,19 @@ int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int
     return fail(SS_ERR_INVALID, "ss_render: rgb, depth and seg must be 4-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_render(env->P, env->kind, env_ids, m, width, height, *cam, rgb, depth, seg, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_kinematics(ss_env* env, const int32_t* env_ids, int32_t m, float* body_twist, float* summary, float* corners, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_kinematics: m must be >= 0");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_kinematics: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (!body_twist && !summary && !corners) return fail(SS_ERR_INVALID, "ss_kinematics: body_twist, summary and corners are all NULL");
+  if (((uintptr_t)body_twist | (uintptr_t)summary | (uintptr_t)corners) & 15)
+    return fail(SS_ERR_INVALID, "ss_kinematics: body_twist, summary and corners must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_kinematics(env->P, env->kind, env_ids, m, body_twist, summary, corners, (hipStream_t)stream));
   return SS_OK;
 }
 

@@ -64,9 +64,11 @@ SSD void normalize3(float v[3]) {
 }
 
 // World pose of body b of env e (docs/RENDER.md 2; the frame convention of model.fk): out = position (3) | R row-major (9).  The lane walks
-// its body's ancestor chain from the root, so the 22 bodies of an env are 22 independent lanes.
-template <class Model>
-SSD void body_pose(const Params& P, int e, int b, float out[12]) {
+// its body's ancestor chain from the root, so the 22 bodies of an env are 22 independent lanes.  through(j, R) is called once per joint j
+// of the chain, root first, with the world orientation R of the joint's PARENT body, before the joint moves the pose on to its child
+// (ss_kinematics.hpp carries the twist along the chain with it; body_pose below passes nothing).
+template <class Model, class Through>
+SSD void walk_chain(const Params& P, int e, int b, float out[12], Through&& through) {
   const float* F = P.fstate + e;
   const size_t np = (size_t)P.npad;
   float quat[4], p[3], R[3][3];
@@ -79,6 +81,7 @@ SSD void body_pose(const Params& P, int e, int b, float out[12]) {
 #pragma unroll 1
   for (int k = depth - 1; k >= 0; --k) {
     const int j = chain[k] - 1;
+    through(j, R);
     const float rj[3] = {Model::r[j][0], Model::r[j][1], Model::r[j][2]};
     for (int i = 0; i < 3; ++i) p[i] += R[i][0] * rj[0] + R[i][1] * rj[1] + R[i][2] * rj[2];
     float s, c;
@@ -93,6 +96,10 @@ SSD void body_pose(const Params& P, int e, int b, float out[12]) {
   for (int i = 0; i < 3; ++i) out[i] = p[i];
   for (int i = 0; i < 3; ++i)
     for (int k = 0; k < 3; ++k) out[3 + 3 * i + k] = R[i][k];
+}
+template <class Model>
+SSD void body_pose(const Params& P, int e, int b, float out[12]) {
+  walk_chain<Model>(P, e, b, out, [](int, const float (&)[3][3]) {});
 }
 
 // robot primitive k, placed by the pose of its body (poses: [22][12] as body_pose writes them)

@@ -5,7 +5,12 @@
 
 --net takes a file written by ppo.save_checkpoint (or a bare ActorCritic state_dict), or a reference legacy .pt checkpoint
 (legacy_checkpoint.load_reference_checkpoint).  The K envs are tiled into one frame per control step.  --out ending in .gif is written
-with PIL when it is importable; otherwise, and for --out *.npy, the frames are saved as one [T, H, W, 3] uint8 array."""
+with PIL when it is importable; otherwise, and for --out *.npy, the frames are saved as one [T, H, W, 3] uint8 array.
+
+--trace FILE.npz also writes what the frames show as numbers (SteppingStoneVecEnv.kinematics, docs/PHYSICS.md 9), one entry per control
+step and env, for the state each step ends in: com [T,K,3], com_vel [T,K,3], corner_height [T,K,8] (sole corners over the target stone's
+surface plane), corner_carrier [T,K,8] (the stone slot that carries each corner, -1: none), contact [T,K,2] (the observation's foot
+contact flags, right / left), next_step_index [T,K], done [T,K]."""
 import argparse
 import math
 import os
@@ -45,9 +50,13 @@ def tile(frames):
     return out
 
 
+TRACE_KEYS = ("com", "com_vel", "corner_height", "corner_carrier")
+
+
 def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240), camera="track", device="cuda:0", out=None,
-        log=print):
-    """Roll the policy out deterministically; returns the [T, H, W, 3] uint8 animation (and writes it to `out` if given)."""
+        log=print, trace=None):
+    """Roll the policy out deterministically; returns the [T, H, W, 3] uint8 animation (and writes it to `out` if given; the kinematic
+    trace of the module docstring to `trace` if given)."""
     ac = load_policy(net, device)
     ac.eval()
     env = SteppingStoneVecEnv(env_id, envs, seed=seed, device=device, return_numpy=False)
@@ -57,6 +66,7 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
     log("Env: {}".format(env_id))
     log("Model: {}".format(os.path.basename(net)))
     frames = []
+    rec = {k: [] for k in TRACE_KEYS + ("contact", "next_step_index", "done")}
     try:
         obs = env.reset()
         ep_reward = torch.zeros(envs, dtype=torch.float64, device=env.device)
@@ -66,6 +76,13 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
                 _, action, _ = ac.act(obs, deterministic=True)
             obs, rew, done, _ = env.step(action)
             ep_reward += rew.double()
+            if trace:
+                kin = env.kinematics(twists=False)
+                for k in TRACE_KEYS:
+                    rec[k].append(kin[k].cpu().numpy())
+                rec["contact"].append(obs[:, 48:50].cpu().numpy() > 0.5)
+                rec["next_step_index"].append(env.next_step_index)
+                rec["done"].append(done.cpu().numpy().astype(bool))
             if bool(done.any()):
                 for i in torch.nonzero(done).flatten().tolist():
                     log("Episode reward: {}".format(float(ep_reward[i])) + ("" if envs == 1 else "  (env {})".format(i)))
@@ -73,6 +90,11 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
     finally:
         env.close()
     anim = np.stack(frames)
+    if trace:
+        if not trace.endswith(".npz"):
+            trace += ".npz"
+        np.savez(trace, **{k: np.stack(v) for k, v in rec.items()})
+        log("wrote %s (%d steps x %d envs)" % (trace, len(rec["done"]), envs))
     if out:
         save(anim, out, log)
     return anim
@@ -109,9 +131,10 @@ def main(argv=None):
     p.add_argument("--camera", choices=("track", "chase"), default="track")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--out", default="enjoy.gif", help=".gif (needs PIL) or .npy")
+    p.add_argument("--trace", default=None, metavar="FILE.npz", help="also write COM, sole-corner heights / carriers, contact flags per step")
     a = p.parse_args(argv)
     w, h = (int(x) for x in a.size.lower().split("x"))
-    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out)
+    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out, trace=a.trace)
     return 0
 
 

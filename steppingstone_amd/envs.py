@@ -167,6 +167,12 @@ class HipBackend:
     def body_poses(self, out):
         _lib.check(self.lib.ss_body_poses(self.h, _ptr(out), _stream(self.device)))
 
+    def kinematics(self, env_ids, m, body_twist, summary, corners):
+        """env_ids: int32 device tensor [m], or None for envs 0..m-1 (m == N); body_twist [m,22,6] / summary [m,12] / corners [m,8,8]:
+        float32 device tensors or None, not all three (docs/PHYSICS.md 9)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_kinematics(self.h, opt(env_ids), int(m), opt(body_twist), opt(summary), opt(corners), _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
@@ -453,6 +459,42 @@ class SteppingStoneVecEnv:
         out = torch.empty((self.num_envs, _lib.NUM_BODIES, 12), dtype=torch.float32, device=self.device)
         self.backend.body_poses(out)
         return out.cpu().numpy() if self.return_numpy else out
+
+    def kinematics(self, env_ids=None, twists=True, summary=True, corners=True):
+        """Whole-body kinematics of the envs env_ids names (default: all; the forms of get_state()), read on the GPU from the current
+        state (docs/PHYSICS.md 9; world frame).  Returns a dict of tensors on the env's device (numpy arrays in numpy mode), m rows in
+        env_ids order, holding the groups asked for:
+          twists:  body_twist [m,22,6]: angular velocity | velocity of the link frame's origin, per body of body_poses();
+          summary: com [m,3], com_vel [m,3], ang_mom [m,3] (about the centre of mass), kinetic [m] (rigid bodies only, no rotor armature),
+                   potential [m], mass [m];
+          corners: corner_pos [m,8,3], corner_vel [m,8,3], corner_height [m,8] (signed height over the target stone's surface plane,
+                   negative below it), corner_carrier [m,8] int32 (0 / 1 / 2: carried by stone n-1 / n / n+1, -1: by none); corner
+                   4 * foot + k, foot 0 = right."""
+        if not hasattr(self.backend, "kinematics"):
+            raise NotImplementedError("this backend has no kinematic readout")
+        if not (twists or summary or corners):
+            raise ValueError("kinematics: ask for at least one of twists, summary, corners")
+        if env_ids is None:
+            ids, m = None, self.num_envs
+        else:
+            _, host_ids = self._env_ids(env_ids, allow_mask=False)
+            m = int(host_ids.size)
+            ids = torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        new = lambda *shape: torch.empty((m,) + shape, dtype=torch.float32, device=self.device)
+        bt = new(_lib.NUM_BODIES, 6) if twists else None
+        sm = new(_lib.KIN_SUMMARY) if summary else None
+        co = new(_lib.KIN_CORNER, 8) if corners else None
+        if m:
+            self.backend.kinematics(ids, m, bt, sm, co)
+        out = {}
+        if twists:
+            out["body_twist"] = bt
+        if summary:
+            out.update(com=sm[:, 0:3], com_vel=sm[:, 3:6], ang_mom=sm[:, 6:9], kinetic=sm[:, 9], potential=sm[:, 10], mass=sm[:, 11])
+        if corners:
+            out.update(corner_pos=co[:, :, 0:3], corner_vel=co[:, :, 3:6], corner_height=co[:, :, 6],
+                       corner_carrier=co[:, :, 7].to(torch.int32))
+        return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
 
     @property
     def unwrapped(self):
