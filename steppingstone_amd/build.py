@@ -118,6 +118,26 @@ def build_probe(force=False, verbose=False):
     return PROBE_LIB
 
 
+PROBE_PK_LIB = os.path.join(LIBDIR, "libss_probe_pk.so")
+PROBE_PK_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe_pk.hip")
+
+
+def build_probe_pk(force=False, verbose=False):
+    """lib/libss_probe_pk.so from tests/device/ss_probe_pk.hip: the half-broadcast packed multiply(-add) of ss_pair.hpp beside scalar
+    fmaf, and the joint-limit / joint-torque forms of ss_dynamics.hpp beside the forms they replaced, compiled with the product's
+    FLAGS.  TEST BUILD -- tests/test_pair_broadcast.py and tests/test_limit_forms.py require bitwise agreement; nothing in the
+    package loads it."""
+    deps = [PROBE_PK_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and os.path.exists(PROBE_PK_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_PK_LIB) for d in deps if os.path.exists(d)):
+        return PROBE_PK_LIB
+    os.makedirs(LIBDIR, exist_ok=True)
+    cmd = [hipcc()] + FLAGS + ["-shared", PROBE_PK_SRC, "-o", PROBE_PK_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return PROBE_PK_LIB
+
+
 def build_variant(name, extra_flags, verbose=False):
     """var/libss_<name>.so: the product recipe plus extra_flags.  A tuning build: nothing in the package loads it (point
     STEPPINGSTONE_LIB at it: tools/ab_libs.sh, tools/state_hash.py, tools/sched_fuzz.py)."""

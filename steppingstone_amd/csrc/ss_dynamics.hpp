@@ -62,6 +62,9 @@ constexpr int kHandJc = 0, kHandL0 = kHandJc + 8 * kRecWords, kHandLc = kHandL0 
 // #0b and #1 (three-helper variant): 4 x 6 floats in the place of the spine joint records, which the main wavefront writes only
 // at the end of the #1 -> #2 window (after it has read the biases).
 constexpr bool bias_offload(int helpers) { return helpers >= 3; }
+// The spine joints' A and C blocks as one pair on packed instructions (pass 2; ss_pair.hpp's sym_pack / xinertia_ac) in the three-helper
+// kernels, where the spine + base window is the main wavefront's own.  Values are the same either way.
+constexpr bool spine_packed(int helpers) { return helpers >= 3; }
 constexpr int kHandBias = kHandJc;
 static_assert(24 <= 3 * kRecWords, "biases fit the spine records' place");
 constexpr int kHandRows = kHandJc + 3 * kRecWords;
@@ -835,6 +838,36 @@ __device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&&
 }
 #endif
 
+// Joint limit of joint J (PHYSICS.md 3.1): how far q is outside [lo, hi] (signed, 0 inside) and the limit's gains, which are 0 inside.
+//   viol: min(q - lo, 0) + max(q - hi, 0) is q < lo ? q - lo : (q > hi ? q - hi : 0) for every float q -- lo < hi, so at most one
+//         term is non-zero, the other adds an exact 0, a NaN gives 0 both ways (fminf / fmaxf return the other operand) -- and takes
+//         both bounds as VOP2 literals where the comparisons needed an s_mov_b32 each;
+//   kl, dl: K's bits under a mask that is all ones outside the range and 0 inside are "viol != 0 ? K : 0" exactly, and K then is the
+//         literal of a v_and_b32 where each select needed a v_mov_b32 of K first (the mask is made opaque, or the optimiser turns
+//         the masking back into the two selects).
+// Four instructions fewer per joint; tests/test_limit_forms.py holds these forms against the ones they replaced, bitwise.
+template <class Model, int J>
+SSD void joint_limit(float q, float& viol, float& kl, float& dl) {
+  constexpr float lo = Model::lo[J], hi = Model::hi[J], klim = Model::klim[J], dlim = Model::dlim[J];
+  static_assert(lo < hi, "a joint's range is not empty");
+  viol = fminf(q - lo, 0.f) + fmaxf(q - hi, 0.f);
+  uint32_t m = viol != 0.f ? 0xFFFFFFFFu : 0u;
+  SS_REG(m);
+  kl = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, klim) & m);
+  dl = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, dlim) & m);
+}
+
+// explicit joint torque and implicit diagonal of joint J (PHYSICS.md 3.1)
+template <class Model, int J>
+SSD void joint_tau(float power, float q, float qd, float act, float& tau, float& Dadd) {
+  constexpr float h = kH;
+  constexpr float kd = Model::damping[J], ks = Model::stiffness[J], arm = Model::armature[J], tq = Model::torque[J];
+  float viol, kl, dl;
+  joint_limit<Model, J>(q, viol, kl, dl);
+  tau = power * tq * act - kd * qd - ks * (q + h * qd) - kl * (viol + h * qd) - dl * qd;
+  Dadd = arm + h * (kd + dl) + (h * h) * (ks + kl);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // State (q, qd, base pose/twist), stones and clipped actions of THIS lane's world live in LDS (region B).
 template <class Model, int HELPERS = 0>
@@ -853,16 +886,8 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
 #pragma unroll
   for (int k = 0; k < NH; ++k) { q_all[k] = L.s(S_Q + k); qd_all[k] = L.s(S_QD + k); act_all[k] = L.s(S_ACT + k); }
   SS_MEMBAR();
-  // explicit joint torque and implicit diagonal of joint j (PHYSICS.md 3.1)
   auto joint_tau = [&](auto Jc, float q, float qd, float act, float& tau, float& Dadd) {
-    constexpr int j = decltype(Jc)::value;
-    constexpr float lo = Model::lo[j], hi = Model::hi[j], kd = Model::damping[j], ks = Model::stiffness[j];
-    constexpr float klim = Model::klim[j], dlim = Model::dlim[j], arm = Model::armature[j], tq = Model::torque[j];
-    float viol = q > hi ? q - hi : (q < lo ? q - lo : 0.f);
-    bool lim = viol != 0.f;
-    float kl = lim ? klim : 0.f, dl = lim ? dlim : 0.f;
-    tau = power * tq * act - kd * qd - ks * (q + h * qd) - kl * (viol + h * qd) - dl * qd;
-    Dadd = arm + h * (kd + dl) + (h * h) * (ks + kl);
+    ss::joint_tau<Model, decltype(Jc)::value>(power, q, qd, act, tau, Dadd);
   };
   float tau_pre[NH], dadd_pre[NH];     // helper variant: the joint torques here, while the helpers evaluate cos / sin
   if constexpr (cs_offload(HELPERS) && HELPERS > 0) {
@@ -948,12 +973,28 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       r.u = tau - pA.w[ax];
       const float* Uw = r.Uw;
       const float* Uv = r.Uv;
-      float sw[3] = {r.Dinv * Uw[0], r.Dinv * Uw[1], r.Dinv * Uw[2]};
-      float sv[3] = {r.Dinv * Uv[0], r.Dinv * Uv[1], r.Dinv * Uv[2]};
-      I.A.m[0] -= sw[0] * Uw[0]; I.A.m[1] -= sw[1] * Uw[1]; I.A.m[2] -= sw[2] * Uw[2];
-      I.A.m[3] -= sw[0] * Uw[1]; I.A.m[4] -= sw[0] * Uw[2]; I.A.m[5] -= sw[1] * Uw[2];
-      I.C.m[0] -= sv[0] * Uv[0]; I.C.m[1] -= sv[1] * Uv[1]; I.C.m[2] -= sv[2] * Uv[2];
-      I.C.m[3] -= sv[0] * Uv[1]; I.C.m[4] -= sv[0] * Uv[2]; I.C.m[5] -= sv[1] * Uv[2];
+      // the spine joints (three helpers): A and C as one pair {A, C} through the rank-one update and, below, the rotation
+      constexpr bool kPairAC = spine_packed(HELPERS) && j < 3;
+      Sym3P AC;
+      float sw[3];
+      if constexpr (kPairAC) {
+        AC = sym_pack(I.A, I.C);
+        const ssf2 U2[3] = {pkv(Uw[0], Uv[0]), pkv(Uw[1], Uv[1]), pkv(Uw[2], Uv[2])};
+        const ssf2 D2 = {r.Dinv, r.Dinv};
+        const ssf2 s2[3] = {D2 * U2[0], D2 * U2[1], D2 * U2[2]};
+        AC.m[0] -= s2[0] * U2[0]; AC.m[1] -= s2[1] * U2[1]; AC.m[2] -= s2[2] * U2[2];
+        AC.m[3] -= s2[0] * U2[1]; AC.m[4] -= s2[0] * U2[2]; AC.m[5] -= s2[1] * U2[2];
+#pragma unroll
+        for (int m = 0; m < 6; ++m) { I.A.m[m] = AC.m[m].x; I.C.m[m] = AC.m[m].y; }
+        sw[0] = s2[0].x; sw[1] = s2[1].x; sw[2] = s2[2].x;
+      } else {
+        sw[0] = r.Dinv * Uw[0]; sw[1] = r.Dinv * Uw[1]; sw[2] = r.Dinv * Uw[2];
+        float sv[3] = {r.Dinv * Uv[0], r.Dinv * Uv[1], r.Dinv * Uv[2]};
+        I.A.m[0] -= sw[0] * Uw[0]; I.A.m[1] -= sw[1] * Uw[1]; I.A.m[2] -= sw[2] * Uw[2];
+        I.A.m[3] -= sw[0] * Uw[1]; I.A.m[4] -= sw[0] * Uw[2]; I.A.m[5] -= sw[1] * Uw[2];
+        I.C.m[0] -= sv[0] * Uv[0]; I.C.m[1] -= sv[1] * Uv[1]; I.C.m[2] -= sv[2] * Uv[2];
+        I.C.m[3] -= sv[0] * Uv[1]; I.C.m[4] -= sv[0] * Uv[2]; I.C.m[5] -= sv[1] * Uv[2];
+      }
 #pragma unroll
       for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -972,7 +1013,8 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
           pa.v[rr] = pA.v[rr] + I.B[ai][rr] * cwi + I.B[aj][rr] * cwj + Cf[rr][ai] * cvi + Cf[rr][aj] * cvj + Uv[rr] * du;
         }
       }
-      Ip = xinertia<Model, j>(r.cs, r.sn, I);
+      if constexpr (kPairAC) Ip = xinertia_ac<Joint<Model, j>>(r.cs, r.sn, AC, I.B);
+      else Ip = xinertia<Model, j>(r.cs, r.sn, I);
       pp = xforce<Model, j>(r.cs, r.sn, pa);
     };
     JRec2 jr2[4];             // joints (3,13) (4,14) (5,15) (6,16)
@@ -1295,14 +1337,16 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       static_for<0, 12>([&](auto Rc) {
         constexpr int row = decltype(Rc)::value, k = row / 3;
         const bool on = (active >> k) & 1;
-        const float w[6] = {rWp[row][0].x, rWp[row][0].y, rWp[row][1].x, rWp[row][1].y, rWp[row][2].x, rWp[row][2].y};
+        // w[b] is half b & 1 of the pair rWp[row][b >> 1]: taken from there by the instruction itself (pk_fma_half: the odd columns
+        // cost a v_mov_b32 each otherwise, 36 per substep)
         ssf2 y[3];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) y[i] = Lc[0][i] * ssf2{w[0], w[0]};
+        for (int i = 0; i < 3; ++i) y[i] = pk_mul_half<0>(Lc[0][i], rWp[row][0]);
+        static_for<1, 6>([&](auto Bc) {
+          constexpr int b = decltype(Bc)::value;
 #pragma unroll
-        for (int b = 1; b < 6; ++b)
-#pragma unroll
-          for (int i = 0; i < 3; ++i) y[i] = Lc[b][i] * ssf2{w[b], w[b]} + y[i];
+          for (int i = 0; i < 3; ++i) y[i] = pk_fma_half<b & 1>(Lc[b][i], rWp[row][b >> 1], y[i]);
+        });
 #pragma unroll
         for (int i = 0; i < 3; ++i) rYp[row][i] = y[i];
         ssf2 acc = rWp[row][0] * y[0];

@@ -248,14 +248,13 @@ SSD void rot_gen(T c, T s, const T M[3][3], T O[3][3]) {
 // articulated inertia of the child (in child coords) -> parent coords:  X^T I X
 //   rotate every block into the parent orientation, then shift the origin by r:
 //   C_p = C', B_p = B' + r x C' (column-wise), A_p[i][j] = A'[i][j] + (r x Bp_row_i)[j] + (r x B'_row_j)[i]
+// (in two steps, so that a caller can rotate A and C some other way: ss_pair.hpp's xinertia_ac)
+//   xinertia_shift: o.A and o.C hold the rotated blocks A' and C' already; rotates B and shifts the origin
 template <class JT, class T>
-SSD ABIT<T> xinertia(T c, T s, const ABIT<T>& I) {
+SSD void xinertia_shift(T c, T s, const T (&B)[3][3], ABIT<T>& o) {
   constexpr int AX = JT::AX;
-  ABIT<T> o;
-  o.A = rot_sym<AX>(c, s, I.A);
-  o.C = rot_sym<AX>(c, s, I.C);
   T Bp[3][3];
-  rot_gen<AX>(c, s, I.B, Bp);
+  rot_gen<AX>(c, s, B, Bp);
   if constexpr (JT::offset) {
     // r x B'_row_j for the three rows of B' (before the shift)
     T rB[3][3];
@@ -284,6 +283,14 @@ SSD ABIT<T> xinertia(T c, T s, const ABIT<T>& I) {
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int b = 0; b < 3; ++b) o.B[a][b] = Bp[a][b];
+}
+template <class JT, class T>
+SSD ABIT<T> xinertia(T c, T s, const ABIT<T>& I) {
+  constexpr int AX = JT::AX;
+  ABIT<T> o;
+  o.A = rot_sym<AX>(c, s, I.A);
+  o.C = rot_sym<AX>(c, s, I.C);
+  xinertia_shift<JT>(c, s, I.B, o);
   return o;
 }
 // the same three through scalar joint J by its number

@@ -23,6 +23,46 @@ SSD ssf2 pk(float a, float b) { return ssf2{a, b}; }          // constants
 #define SS_REG(x) asm("" : "+x"(x))
 #endif
 SSD ssf2 pkv(float a, float b) { SS_REG(a); SS_REG(b); return ssf2{a, b}; }
+// a * {s[H], s[H]} + c and a * {s[H], s[H]}: the factor is one half of a pair that is in registers already.  For the HIGH half the
+// compiler copies it out first (v_mov_b32 tmp, s.hi, then op_sel_hi:[1,0,1] on tmp); the instruction can pick the high dword for
+// both of its halves itself (op_sel:[0,1,0] op_sel_hi:[1,1,1]), which is what the inline assembly says.  The LOW half needs no help.
+// Hazards of the statement: one VALU instruction, registers only.  The compiler treats its result like that of a packed instruction
+// with the src0 op_sel_hi bit set (one wait state before a reader in the next instruction: it pads after the statement) and its
+// operands like any packed instruction's (it pads in front where the producer is of that form); docs/HISTORY.md "Wait states".
+// Values: two fused multiply-adds (two products) of the same operands either way -- tests/test_pair_broadcast.py holds both
+// halves, on the device and in the host build, bitwise against fmaf / the plain product.
+template <int H>
+SSD ssf2 pk_fma_half(ssf2 a, ssf2 s, ssf2 c) {
+  static_assert(H == 0 || H == 1, "low or high half");
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (H == 1) {
+    ssf2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "v"(s), "v"(c));
+    return d;
+  } else {
+    return a * ssf2{s.x, s.x} + c;
+  }
+#else
+  const float f = H ? s.y : s.x;
+  return ssf2{__builtin_fmaf(a.x, f, c.x), __builtin_fmaf(a.y, f, c.y)};
+#endif
+}
+template <int H>
+SSD ssf2 pk_mul_half(ssf2 a, ssf2 s) {
+  static_assert(H == 0 || H == 1, "low or high half");
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (H == 1) {
+    ssf2 d;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(d) : "v"(a), "v"(s));
+    return d;
+  } else {
+    return a * ssf2{s.x, s.x};
+  }
+#else
+  const float f = H ? s.y : s.x;
+  return ssf2{a.x * f, a.y * f};
+#endif
+}
 SSD SV sv_half(const SV2& a, int h) {
   SV o;
 #pragma unroll
@@ -43,6 +83,26 @@ SSD ABI abi_half(const ABIP& a, int h) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) o.B[i][j] = h ? a.B[i][j].y : a.B[i][j].x;
+  return o;
+}
+
+// The A and C blocks of ONE articulated inertia as a pair {A, C}: the joint's rank-one update and the rotation into the parent's
+// orientation apply the same operator to both blocks (ss_dynamics.hpp uses it for the spine joints, whose chain has no twin to pair
+// with).  A packed instruction is two scalar ones of the same operands: every entry keeps its bits.
+SSD Sym3P sym_pack(const Sym3& A, const Sym3& C) {
+  Sym3P o;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) o.m[i] = pkv(A.m[i], C.m[i]);
+  return o;
+}
+// xinertia of ss_math.hpp for a scalar joint, the blocks A and C given as the pair AC
+template <class JT>
+SSD ABI xinertia_ac(float c, float s, const Sym3P& AC, const float (&B)[3][3]) {
+  const Sym3P R = rot_sym<JT::AX>(ssf2{c, c}, ssf2{s, s}, AC);
+  ABI o;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { o.A.m[i] = R.m[i].x; o.C.m[i] = R.m[i].y; }
+  xinertia_shift<JT>(c, s, B, o);
   return o;
 }
 
