@@ -1,7 +1,8 @@
 // ss_probe.hip -- calls the step kernels' spatial algebra (ss_math.hpp, ss_pair.hpp, the per-joint helpers of ss_dynamics.hpp) one
 // operator at a time, one case per lane, so that tests/test_spatial_ops.py can hold each operator against the fp64 reference of
 // tests/np_spatial.py; and, the same way, the contact stage of ss_dynamics.hpp (detection, Jacobian rows, contact-space operators) and
-// the env formulas of ss_kernels.hpp (sampler, observation terms, reset noise) for tests/test_contact_ops.py / tests/np_contact_ops.py.
+// the env formulas of ss_kernels.hpp (sampler, observation terms, reset noise) for tests/test_contact_ops.py / tests/np_contact_ops.py;
+// and one whole substep<Model, 0> on the lane pair of a robot for tests/test_substep.py / tests/substep_cases.py.
 // TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
 //
 // The same source is compiled two ways:
@@ -9,7 +10,8 @@
 //     takes DEVICE pointers and a stream, launches whole wavefronts of 64 (the lane exchange needs every lane active) and guards
 //     only its stores by n;
 //   * for the CPU by tests/probe_lib.py (-DSS_PROBE_HOST, hipcc --cuda-host-only); ssp_run loops over the cases with host pointers.
-//     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED.
+//     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED, and every other op sees the identity -- but `substep`,
+//     whose two lanes run as two threads that meet at every exchange.
 //
 //   int ssp_run(int op, int kind, int n, const float* in, float* out, void* stream)
 //     in [n][IN_W(op)], out [n][OUT_W(op)], row-major; kind 0 = ModelWalker3D, 1 = ModelMike.  Joint / body / pair numbers are
@@ -29,7 +31,37 @@
 #include "../../steppingstone_amd/csrc/ss_kernels.hpp"
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-float ss_host_xchg(float x) { return x; }      // the identity: contact_ops forms C with the lane as its own partner (the exchange op itself is refused)
+#include <atomic>
+#include <thread>
+// The lane exchange on the host.  Every op but `substep` runs one lane per case on the calling thread, which has no partner: the
+// exchange is the identity (contact_ops forms C with the lane as its own partner; the exchange op itself is refused).  `substep` runs
+// the two lanes of a robot as two threads that meet at every exchange, as tests/host/host_harness.cpp's lanes do.
+namespace {
+struct PairSync {
+  std::atomic<int> arrived{0}, generation{0};
+  float slot[2];
+  void wait() {
+    const int g = generation.load(std::memory_order_acquire);
+    if (arrived.fetch_add(1, std::memory_order_acq_rel) == 1) {
+      arrived.store(0, std::memory_order_relaxed);
+      generation.store(g + 1, std::memory_order_release);
+    } else {
+      while (generation.load(std::memory_order_acquire) == g) std::this_thread::yield();
+    }
+  }
+};
+thread_local PairSync* t_sync = nullptr;      // null: no partner
+thread_local int t_side = 0;
+}  // namespace
+float ss_host_xchg(float x) {
+  PairSync* s = t_sync;
+  if (!s) return x;
+  s->slot[t_side] = x;
+  s->wait();
+  const float r = s->slot[1 - t_side];
+  s->wait();
+  return r;
+}
 void ss_host_wave_sync() {}
 #endif
 
@@ -83,6 +115,12 @@ enum {
                        //                                          -> roll, pitch, cy, sy (quat); target_features 5 (given cy, sy); planar_dist(stone, pos);
                        //                                             clip5(x); obs_angle 21; obs_rate 21; reset_angle 21; reset_angle 21 over
                        //                                             ClampModel (below), whose draws reach the clamps
+  // ---- one whole substep.  One case is one ROBOT = two lanes (2i: the right half, 2i + 1: the left half in its y-mirrored world); the row
+  // is the robot's, in the true world, and each lane takes its half of it the way step_env does.
+  OP_SUBSTEP,          // [pos 3, quat 4, w 3, v 3, q 21, qd 21, act 21 (clipped, policy coordinates), power, (centre 3, normal 3, cos, sin of the
+                       //  heading) x stones n-1, n, n+1, (warm key, lam 12) x right foot, left foot (each in its lane's world), calls (1 or 2)]
+                       //                                          -> per lane, the raw LDS words after `calls` x substep<Model, 0>: q 12, qd 12, pos 3,
+                       //                                             quat 4, w 3, v 3; Warm: key, lam 12; FootReport: contact, on_target, sole 3
   OP_COUNT
 };
 enum { SSP_BAD_OP = -1, SSP_UNSUPPORTED = -2, SSP_BAD_KIND = -3 };
@@ -122,10 +160,13 @@ __host__ __device__ constexpr int in_w(int op) {
     case OP_SAMPLER: return SS_NCELL + 1 + 8 + 3;
     case OP_WINDOW_PROB: return 2;
     case OP_OBS_TERMS: return 15 + 2 * NJ + 24;
+    case OP_SUBSTEP: return 13 + 3 * NJ + 1 + 24 + 2 * 13 + 1;
     default: return 0;
   }
 }
 __host__ __device__ constexpr bool needs_lds(int op) { return op >= OP_FK_DETECT; }
+__host__ __device__ constexpr int lanes_per_case(int op) { return op == OP_SUBSTEP ? 2 : 1; }      // out_w is per case: lanes x words
+constexpr int kSubOut = 2 * NH + 13 + 13 + 5;
 __host__ __device__ constexpr int out_w(int op) {
   switch (op) {
     case OP_ROT: return 6;
@@ -161,6 +202,7 @@ __host__ __device__ constexpr int out_w(int op) {
     case OP_SAMPLER: return 2 + 22 + 3 + 3;
     case OP_WINDOW_PROB: return SS_NCELL;
     case OP_OBS_TERMS: return 11 + 4 * NJ;
+    case OP_SUBSTEP: return 2 * kSubOut;
     default: return 0;
   }
 }
@@ -671,20 +713,91 @@ SSD void run_case(const float* p, float* o, const Lds& L) {
       o[11 + 2 * NJ + j] = reset_angle<Model, j>(r);
       o[11 + 3 * NJ + j] = reset_angle<ClampModel, j>(r);
     });
+  } else if constexpr (OP == OP_SUBSTEP) {
+    // the lane's state as step_env leaves it in LDS before its substeps (ss_kernels.hpp, steps 1 and 2 of step_env)
+    const int side = L.lane & 1;
+    const float m = side ? -1.f : 1.f;
+    put_base(L, m, p, p + 3, p + 7, p + 10);
+    float qin[NH], qdin[NH];
+    static_for<0, NH>([&](auto Kc) {
+      constexpr int k = decltype(Kc)::value, jr = kHalf[k], jl = left_twin(jr);
+      const int gj = side ? jl : jr;
+      qin[k] = p[13 + gj];
+      qdin[k] = p[13 + NJ + gj];
+      L.s(S_ACT + k) = action_lane_sign(jr, m) * p[13 + 2 * NJ + gj];
+    });
+    put_joints(L, m, qin, qdin);
+    const float power = p[13 + 3 * NJ];
+    const float* st = p + 14 + 3 * NJ;
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+      L.s(S_STP + sl * 3 + 0) = st[sl * 8 + 0]; L.s(S_STP + sl * 3 + 1) = m * st[sl * 8 + 1]; L.s(S_STP + sl * 3 + 2) = st[sl * 8 + 2];
+      L.s(S_STN + sl * 3 + 0) = st[sl * 8 + 3]; L.s(S_STN + sl * 3 + 1) = m * st[sl * 8 + 4]; L.s(S_STN + sl * 3 + 2) = st[sl * 8 + 5];
+      L.q2(kLdsHead + sl) = make_float2(st[sl * 8 + 6], m * st[sl * 8 + 7]);
+    }
+    const float* wp = st + 24 + 13 * side;
+    Warm wm;
+    wm.key = (int)wp[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) wm.lam[k][d] = wp[1 + 3 * k + d];
+    if constexpr (warm_in_lds(0)) {      // where the plain variant keeps it between the substeps
+      L.s(S_WKEY) = __builtin_bit_cast(float, wm.key);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) L.s(S_WLAM + 3 * k + d) = wm.lam[k][d];
+    }
+    const int calls = (int)st[24 + 26];
+    FootReport fr = {};
+#pragma unroll 1
+    for (int c = 0; c < calls; ++c) substep<Model, 0>(power, fr, L, wm);
+    if constexpr (warm_in_lds(0)) {
+      wm.key = __builtin_bit_cast(int, L.s(S_WKEY));
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) wm.lam[k][d] = L.s(S_WLAM + 3 * k + d);
+    }
+#pragma unroll
+    for (int k = 0; k < NH; ++k) { o[k] = L.s(S_Q + k); o[NH + k] = L.s(S_QD + k); }
+    o += 2 * NH;
+#pragma unroll
+    for (int i = 0; i < 13; ++i) o[i] = L.s(S_POS + i);      // S_POS 3, S_QUAT 4, S_VW 3, S_VV 3 are consecutive
+    static_assert(S_QUAT == S_POS + 3 && S_VW == S_QUAT + 4 && S_VV == S_VW + 3 && S_STP == S_VV + 3, "the base words are consecutive");
+    o += 13;
+    o[0] = (float)wm.key;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) o[1 + 3 * k + d] = wm.lam[k][d];
+    o += 13;
+    o[0] = (float)fr.contact; o[1] = (float)fr.on_target;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[2 + i] = fr.sole[i];
   }
 }
 
 #if !defined(SS_PROBE_HOST)
-// one wavefront per workgroup, one case per lane.  Lanes past n redo case n - 1 (every lane stays active and reads inside the
-// buffer); only lanes below n store.
+// one wavefront per workgroup, one case per lane (`substep`: per lane pair; a lane's share of the output row is OW words).  Lanes past
+// the last case redo case n - 1 (every lane stays active and reads inside the buffer; a lane keeps its side, so a pair stays a pair); only
+// lanes of a case below n store.
 template <class Model, int OP>
 __global__ __launch_bounds__(kWave) void probe_kernel(int n, const float* __restrict__ in, float* __restrict__ out) {
-  constexpr int IW = in_w(OP), OW = out_w(OP);
+  constexpr int LPC = lanes_per_case(OP), IW = in_w(OP), OW = out_w(OP) / LPC;
   const int idx = blockIdx.x * kWave + threadIdx.x;
-  const int src = idx < n ? idx : n - 1;
-  float row[IW], o[OW];
+  const int cas = idx / LPC;
+  const int src = cas < n ? cas : n - 1;
+  float o[OW];
+  // `substep` reads its row where it lies: 128 words held in registers across the call would only spill
+  float rowbuf[LPC == 1 ? IW : 1];
+  const float* row = in + (size_t)src * IW;
+  if constexpr (LPC == 1) {
 #pragma unroll
-  for (int i = 0; i < IW; ++i) row[i] = in[(size_t)src * IW + i];
+    for (int i = 0; i < IW; ++i) rowbuf[i] = in[(size_t)src * IW + i];
+    row = rowbuf;
+  }
 #pragma unroll
   for (int i = 0; i < OW; ++i) o[i] = 0.f;
   Lds L = {nullptr, (int)threadIdx.x};
@@ -693,7 +806,7 @@ __global__ __launch_bounds__(kWave) void probe_kernel(int n, const float* __rest
     L.base = reinterpret_cast<float*>(lds);
   }
   run_case<Model, OP>(row, o, L);
-  if (idx < n) {
+  if (cas < n) {
 #pragma unroll
     for (int i = 0; i < OW; ++i) out[(size_t)idx * OW + i] = o[i];
   }
@@ -716,7 +829,20 @@ int run(int op, int n, const float* in, float* out, void* stream) {
       float o[out_w(OP)];
       for (int i = 0; i < out_w(OP); ++i) o[i] = 0.f;
       for (float& x : lds) x = std::numeric_limits<float>::quiet_NaN();
-      run_case<Model, OP>(in + (size_t)e * in_w(OP), o, L);
+      if constexpr (lanes_per_case(OP) == 2) {      // lanes 0 and 1 of the block, two threads that meet at every exchange
+        PairSync sync;
+        auto lane = [&](int side) {
+          t_sync = &sync;
+          t_side = side;
+          run_case<Model, OP>(in + (size_t)e * in_w(OP), o + side * (out_w(OP) / 2), Lds{lds.data(), side});
+          t_sync = nullptr;
+        };
+        std::thread partner(lane, 1);
+        lane(0);
+        partner.join();
+      } else {
+        run_case<Model, OP>(in + (size_t)e * in_w(OP), o, L);
+      }
       for (int i = 0; i < out_w(OP); ++i) out[(size_t)e * out_w(OP) + i] = o[i];
     }
     rc = 0;
@@ -725,7 +851,7 @@ int run(int op, int n, const float* in, float* out, void* stream) {
       rc = SSP_UNSUPPORTED;
     } else {
       (void)hipGetLastError();      // what this call returns speaks of this launch alone
-      probe_kernel<Model, OP><<<dim3((n + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream>>>(n, in, out);
+      probe_kernel<Model, OP><<<dim3((n * lanes_per_case(OP) + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream>>>(n, in, out);
       rc = -(int)hipGetLastError();
     }
 #endif

@@ -1,5 +1,5 @@
-"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage and env formulas behind one C entry, one
-operator per call.
+"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas and one whole substep
+behind one C entry, one operator per call.
     host flavour:   compiled here for the CPU (hipcc --cuda-host-only) into tests/host/libss_probe_host.so, numpy pointers;
     device flavour: steppingstone_amd/lib/libss_probe.so, built for gfx950 by steppingstone_amd.build.build_probe(), torch tensors.
 TEST INFRASTRUCTURE; never imported by steppingstone_amd."""
@@ -20,7 +20,7 @@ CSRC = os.path.join(ROOT, "steppingstone_amd", "csrc")
 OPS = ["rot", "rot2", "cross_r", "cross_rP", "xmotion", "xforce", "xmotionP", "xforceP", "xinertia", "xinertiaP", "abi_body",
        "abi_add_bodyP", "body_bias", "body_biasP", "imp_up", "imp_down", "imp_down_pair", "imp_up_pair", "imp_down_pair_loaded",
        "aba_acc", "aba_accP", "quat_rot", "mirror_sv", "abi_dense", "pack", "sincos", "chol", "xchg", "philox",
-       "fk_detect", "jacobian_rows", "contact_ops", "sampler", "window_prob", "obs_terms"]
+       "fk_detect", "jacobian_rows", "contact_ops", "sampler", "window_prob", "obs_terms", "substep"]
 OP = {name: i for i, name in enumerate(OPS)}
 UNSUPPORTED = -2
 
@@ -39,7 +39,7 @@ def build_host(src=SRC, lib=HOST_LIB, csrc=CSRC):
     if host_ready(src, lib, csrc):
         return lib
     subprocess.check_call([hipcc(), "--cuda-host-only", "-x", "hip", "-O1", "-std=c++17", "-fno-signed-zeros", "-ffp-contract=on",
-                           "-fPIC", "-shared", "-fno-math-errno", "-DSS_HOST_HARNESS", "-DSS_PROBE_HOST", src, "-o", lib])
+                           "-fPIC", "-shared", "-pthread", "-fno-math-errno", "-DSS_HOST_HARNESS", "-DSS_PROBE_HOST", src, "-o", lib])
     return lib
 
 
