@@ -138,6 +138,25 @@ def build_probe_pk(force=False, verbose=False):
     return PROBE_PK_LIB
 
 
+PROBE_PAIR_LIB = os.path.join(LIBDIR, "libss_probe_pair.so")
+PROBE_PAIR_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe_pair.hip")
+
+
+def build_probe_pair(force=False, verbose=False):
+    """lib/libss_probe_pair.so from tests/device/ss_probe_pair.hip: the joint torques of a {leg, arm} pair of joints (ss_dynamics.hpp)
+    beside the scalar code they replace, compiled with the product's FLAGS.
+    TEST BUILD -- tests/test_pair_response.py requires bitwise agreement; nothing in the package loads it."""
+    deps = [PROBE_PAIR_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and os.path.exists(PROBE_PAIR_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_PAIR_LIB) for d in deps if os.path.exists(d)):
+        return PROBE_PAIR_LIB
+    os.makedirs(LIBDIR, exist_ok=True)
+    cmd = [hipcc()] + FLAGS + ["-shared", PROBE_PAIR_SRC, "-o", PROBE_PAIR_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return PROBE_PAIR_LIB
+
+
 def build_variant(name, extra_flags, verbose=False):
     """var/libss_<name>.so: the product recipe plus extra_flags.  A tuning build: nothing in the package loads it (point
     STEPPINGSTONE_LIB at it: tools/ab_libs.sh, tools/state_hash.py, tools/sched_fuzz.py)."""

@@ -65,6 +65,12 @@ constexpr bool bias_offload(int helpers) { return helpers >= 3; }
 // The spine joints' A and C blocks as one pair on packed instructions (pass 2; ss_pair.hpp's sym_pack / xinertia_ac) in the three-helper
 // kernels, where the spine + base window is the main wavefront's own.  Values are the same either way.
 constexpr bool spine_packed(int helpers) { return helpers >= 3; }
+// The joint torques of the four {leg, arm} pairs of joints on packed instructions (joint_tau's pair overload) in the three-helper K-step
+// kernel, whose main wavefront's instruction stream is what bounds the step.  Every other kernel keeps the scalar form and is the code it
+// was: the three-helper one-step kernel measured slower with the pair form, the rest compute their torques inside joint_pair with no
+// register to spare (docs/HISTORY.md "Joint torques of the {leg, arm} pairs on packed instructions").  Values are the same either way,
+// bit for bit (tests/test_pair_response.py).
+constexpr bool torques_paired(int helpers, bool kstep) { return helpers >= 3 && kstep; }
 constexpr int kHandBias = kHandJc;
 static_assert(24 <= 3 * kRecWords, "biases fit the spine records' place");
 constexpr int kHandRows = kHandJc + 3 * kRecWords;
@@ -868,9 +874,24 @@ SSD void joint_tau(float power, float q, float qd, float act, float& tau, float&
   Dadd = arm + h * (kd + dl) + (h * h) * (ks + kl);
 }
 
+// the same for the pair of joints JL (leg half) and JA (arm half): the limits per joint (there is no packed min / max / and), the formula
+// once on pairs, term for term as above, so that each half contracts and rounds as the scalar function does
+template <class Model, int JL, int JA>
+SSD void joint_tau(float power, ssf2 q, ssf2 qd, ssf2 act, ssf2& tau, ssf2& Dadd) {
+  constexpr float h = kH;
+  constexpr ssf2 kd = {Model::damping[JL], Model::damping[JA]}, ks = {Model::stiffness[JL], Model::stiffness[JA]};
+  constexpr ssf2 arm = {Model::armature[JL], Model::armature[JA]}, tq = {Model::torque[JL], Model::torque[JA]};
+  float violl, kll, dll, viola, kla, dla;
+  joint_limit<Model, JL>(q.x, violl, kll, dll);
+  joint_limit<Model, JA>(q.y, viola, kla, dla);
+  const ssf2 viol = pkv(violl, viola), kl = pkv(kll, kla), dl = pkv(dll, dla);
+  tau = power * tq * act - kd * qd - ks * (q + h * qd) - kl * (viol + h * qd) - dl * qd;
+  Dadd = arm + h * (kd + dl) + (h * h) * (ks + kl);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // State (q, qd, base pose/twist), stones and clipped actions of THIS lane's world live in LDS (region B).
-template <class Model, int HELPERS = 0>
+template <class Model, int HELPERS = 0, bool KSTEP = false>      // KSTEP: inside a K-step (rollout) kernel
 SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& wm) {
   constexpr float h = kH;
   JointCache jc;
@@ -893,7 +914,16 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
   if constexpr (cs_offload(HELPERS) && HELPERS > 0) {
     static_for<0, NH>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value;
-      joint_tau(std::integral_constant<int, kHalf[k]>{}, q_all[k], qd_all[k], act_all[k], tau_pre[k], dadd_pre[k]);
+      if constexpr (torques_paired(HELPERS, KSTEP) && k >= 3 && k != 7) {
+        if constexpr (k < 7) {           // joints (3 + i, 13 + i) at the leg half's turn: one formula on the pair
+          ssf2 tau2, dadd2;
+          ss::joint_tau<Model, kHalf[k], kHalf[k + 5]>(power, pkv(q_all[k], q_all[k + 5]), pkv(qd_all[k], qd_all[k + 5]),
+                                                       pkv(act_all[k], act_all[k + 5]), tau2, dadd2);
+          tau_pre[k] = tau2.x; tau_pre[k + 5] = tau2.y; dadd_pre[k] = dadd2.x; dadd_pre[k + 5] = dadd2.y;
+        }
+      } else {
+        joint_tau(std::integral_constant<int, kHalf[k]>{}, q_all[k], qd_all[k], act_all[k], tau_pre[k], dadd_pre[k]);
+      }
     });
 #if defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_sched_barrier(0);

@@ -738,7 +738,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   warm_clear(wm);
   if constexpr (warm_in_lds(HELPERS)) L.s(S_WKEY) = 0.f;
 #pragma unroll 1
-  for (int k = 0; k < kNumSubsteps; ++k) substep<Model, HELPERS>(SS_PROF_ARG power, fr, L, wm);
+  for (int k = 0; k < kNumSubsteps; ++k) substep<Model, HELPERS, ROLLOUT>(SS_PROF_ARG power, fr, L, wm);
   SS_FUZZ(0x61u);
   SS_PROF(12);
   SS_MEMBAR();
