@@ -50,12 +50,13 @@ def hipcc():
     return "hipcc"
 
 
+def _up_to_date(lib, deps):
+    """lib exists and no dependency that exists is newer"""
+    return os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps if os.path.exists(d))
+
+
 def stale(lib=LIB):
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
+    return not _up_to_date(lib, [os.path.join(CSRC, s) for s in SOURCES + HEADERS])
 
 
 FUZZ_LIB = os.path.join(LIBDIR, "libsteppingstone_fuzz.so")
@@ -104,11 +105,12 @@ PROBE_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe.hip"
 
 
 def build_probe(force=False, verbose=False):
-    """lib/libss_probe.so from tests/device/ss_probe.hip: the spatial algebra of ss_math.hpp / ss_pair.hpp / ss_dynamics.hpp behind one
-    C entry, one operator per launch, compiled with the product's FLAGS (so the operators round as they do inside the step kernels).
-    TEST BUILD -- tests/test_spatial_ops.py holds every operator against an fp64 reference; nothing in the package loads it."""
-    deps = [PROBE_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and os.path.exists(PROBE_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_LIB) for d in deps if os.path.exists(d)):
+    """lib/libss_probe.so from tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas, one substep
+    and the forms that replaced older ones, behind one C entry, one operator per launch, compiled with the product's FLAGS (so the
+    operators round as they do inside the step kernels).  TEST BUILD -- tests/test_spatial_ops.py, test_contact_ops.py and
+    test_substep.py hold the operators against fp64 references, test_pair_broadcast.py, test_limit_forms.py and test_pair_response.py
+    hold the new forms to the old ones bitwise; nothing in the package loads it."""
+    if not force and _up_to_date(PROBE_LIB, [PROBE_SRC] + [os.path.join(CSRC, h) for h in HEADERS]):
         return PROBE_LIB
     os.makedirs(LIBDIR, exist_ok=True)
     cmd = [hipcc()] + FLAGS + ["-shared", PROBE_SRC, "-o", PROBE_LIB]
@@ -116,45 +118,6 @@ def build_probe(force=False, verbose=False):
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return PROBE_LIB
-
-
-PROBE_PK_LIB = os.path.join(LIBDIR, "libss_probe_pk.so")
-PROBE_PK_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe_pk.hip")
-
-
-def build_probe_pk(force=False, verbose=False):
-    """lib/libss_probe_pk.so from tests/device/ss_probe_pk.hip: the half-broadcast packed multiply(-add) of ss_pair.hpp beside scalar
-    fmaf, and the joint-limit / joint-torque forms of ss_dynamics.hpp beside the forms they replaced, compiled with the product's
-    FLAGS.  TEST BUILD -- tests/test_pair_broadcast.py and tests/test_limit_forms.py require bitwise agreement; nothing in the
-    package loads it."""
-    deps = [PROBE_PK_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and os.path.exists(PROBE_PK_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_PK_LIB) for d in deps if os.path.exists(d)):
-        return PROBE_PK_LIB
-    os.makedirs(LIBDIR, exist_ok=True)
-    cmd = [hipcc()] + FLAGS + ["-shared", PROBE_PK_SRC, "-o", PROBE_PK_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return PROBE_PK_LIB
-
-
-PROBE_PAIR_LIB = os.path.join(LIBDIR, "libss_probe_pair.so")
-PROBE_PAIR_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "ss_probe_pair.hip")
-
-
-def build_probe_pair(force=False, verbose=False):
-    """lib/libss_probe_pair.so from tests/device/ss_probe_pair.hip: the joint torques of a {leg, arm} pair of joints (ss_dynamics.hpp)
-    beside the scalar code they replace, compiled with the product's FLAGS.
-    TEST BUILD -- tests/test_pair_response.py requires bitwise agreement; nothing in the package loads it."""
-    deps = [PROBE_PAIR_SRC] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and os.path.exists(PROBE_PAIR_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_PAIR_LIB) for d in deps if os.path.exists(d)):
-        return PROBE_PAIR_LIB
-    os.makedirs(LIBDIR, exist_ok=True)
-    cmd = [hipcc()] + FLAGS + ["-shared", PROBE_PAIR_SRC, "-o", PROBE_PAIR_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return PROBE_PAIR_LIB
 
 
 def build_variant(name, extra_flags, verbose=False):

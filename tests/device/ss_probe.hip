@@ -2,14 +2,17 @@
 // operator at a time, one case per lane, so that tests/test_spatial_ops.py can hold each operator against the fp64 reference of
 // tests/np_spatial.py; and, the same way, the contact stage of ss_dynamics.hpp (detection, Jacobian rows, contact-space operators) and
 // the env formulas of ss_kernels.hpp (sampler, observation terms, reset noise) for tests/test_contact_ops.py / tests/np_contact_ops.py;
-// and one whole substep<Model, 0> on the lane pair of a robot for tests/test_substep.py / tests/substep_cases.py.
+// and one whole substep<Model, 0> on the lane pair of a robot for tests/test_substep.py / tests/substep_cases.py; and the forms the
+// step kernels use in place of older ones, each beside its reference, for the tests that require the two sides to agree BITWISE: the
+// half-broadcast packed multiply(-add) of ss_pair.hpp (tests/test_pair_broadcast.py), the joint-limit and joint-torque forms of
+// ss_dynamics.hpp (tests/test_limit_forms.py) and joint_tau's {leg, arm} pair overload (tests/test_pair_response.py).
 // TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
 //
 // The same source is compiled two ways:
 //   * for gfx950 by steppingstone_amd/build.py: build_probe() -> steppingstone_amd/lib/libss_probe.so (the product's flags); ssp_run
 //     takes DEVICE pointers and a stream, launches whole wavefronts of 64 (the lane exchange needs every lane active) and guards
 //     only its stores by n;
-//   * for the CPU by tests/probe_lib.py (-DSS_PROBE_HOST, hipcc --cuda-host-only); ssp_run loops over the cases with host pointers.
+//   * for the CPU by tests/probe_lib.py (-DSS_PROBE_HOST, the host recipe of tests/native_build.py); ssp_run loops over the cases with host pointers.
 //     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED, and every other op sees the identity -- but `substep`,
 //     whose two lanes run as two threads that meet at every exchange.
 //
@@ -19,7 +22,7 @@
 //     (Philox, xchg_u32, xchg_i) travel as raw bits.  n == 0 reads and writes nothing and returns IN_W * 1000 + OUT_W, so that the
 //     caller sizes its buffers from the library itself.  Returns 0, or a negative SSP_* / the HIP error of the launch.
 //     An op given a joint number it is not instantiated for (see the lists below) leaves zeros.
-//   The ops from fk_detect on work on a lane-private Lds view as the step kernels do: on the device one __shared__ block of
+//   The ops from fk_detect to substep work on a lane-private Lds view as the step kernels do: on the device one __shared__ block of
 //   kLdsSlots * kWave float4 per wavefront and Lds{base, lane}; on the host one such block per case (filled with NaN first) and lane 0.
 #include <hip/hip_runtime.h>
 
@@ -121,6 +124,16 @@ enum {
                        //  heading) x stones n-1, n, n+1, (warm key, lam 12) x right foot, left foot (each in its lane's world), calls (1 or 2)]
                        //                                          -> per lane, the raw LDS words after `calls` x substep<Model, 0>: q 12, qd 12, pos 3,
                        //                                             quat 4, w 3, v 3; Warm: key, lam 12; FootReport: contact, on_target, sole 3
+  // ---- forms beside their references: the test compares the two sides bitwise.  Every word travels as raw bits (NaN payloads survive).
+  OP_PK_HALF,          // [a.x, a.y, s.x, s.y, c.x, c.y] (kind ignored) -> the form under test, then its scalar reference, 2 floats each:
+                       //                                             fma<0>(a,s,c) fma<1>(a,s,c) fma<0>(a,a,c) fma<1>(a,a,c) mul<0>(a,s) mul<1>(a,s)
+                       //                                             mul<0>(a,a) mul<1>(a,a) | the same eight by fmaf(a.x, f, c.x), fmaf(a.y, f, c.y) /
+                       //                                             a.x * f, a.y * f with f the chosen half.  (a, a): one register as pair and as factor
+  OP_LIMIT_FORMS,      // [power, act, (q, qd) x joints 0..20]      -> per joint 10: viol kl dl tau Dadd of the kernels' forms (joint_limit, joint_tau),
+                       //                                             then of the replaced ones (joint_tau_old below)
+  OP_TAU_PAIR,         // [power, act (leg halves), act (arm halves), (q, qd) x joints 0..20]
+                       //                                          -> per pair (3,13) (4,14) (5,15) (6,16) 8: tau leg, tau arm, Dadd leg, Dadd arm of
+                       //                                             joint_tau's pair overload, then of joint_tau per joint
   OP_COUNT
 };
 enum { SSP_BAD_OP = -1, SSP_UNSUPPORTED = -2, SSP_BAD_KIND = -3 };
@@ -161,10 +174,13 @@ __host__ __device__ constexpr int in_w(int op) {
     case OP_WINDOW_PROB: return 2;
     case OP_OBS_TERMS: return 15 + 2 * NJ + 24;
     case OP_SUBSTEP: return 13 + 3 * NJ + 1 + 24 + 2 * 13 + 1;
+    case OP_PK_HALF: return 6;
+    case OP_LIMIT_FORMS: return 2 + 2 * NJ;
+    case OP_TAU_PAIR: return 3 + 2 * NJ;
     default: return 0;
   }
 }
-__host__ __device__ constexpr bool needs_lds(int op) { return op >= OP_FK_DETECT; }
+__host__ __device__ constexpr bool needs_lds(int op) { return op >= OP_FK_DETECT && op <= OP_SUBSTEP; }
 __host__ __device__ constexpr int lanes_per_case(int op) { return op == OP_SUBSTEP ? 2 : 1; }      // out_w is per case: lanes x words
 constexpr int kSubOut = 2 * NH + 13 + 13 + 5;
 __host__ __device__ constexpr int out_w(int op) {
@@ -203,6 +219,9 @@ __host__ __device__ constexpr int out_w(int op) {
     case OP_WINDOW_PROB: return SS_NCELL;
     case OP_OBS_TERMS: return 11 + 4 * NJ;
     case OP_SUBSTEP: return 2 * kSubOut;
+    case OP_PK_HALF: return 32;
+    case OP_LIMIT_FORMS: return 10 * NJ;
+    case OP_TAU_PAIR: return 32;
     default: return 0;
   }
 }
@@ -301,6 +320,83 @@ struct ClampModel {
   static constexpr float q0[21] = {-0.97f, 0.72f, -0.22f, 1.07f, -1.97f, 0.27f, 0.73f, 0.57f, -0.57f, 1.17f, -0.87f,
                                    1.27f, -0.37f, 2.27f, -2.47f, 0.67f, 0.53f, -0.33f, -0.77f, 0.87f, -0.17f};
 };
+
+// ---- the forms beside their references
+// the scalar reference of the half-broadcast forms: the factor and the operands made opaque one by one, so that each product is
+// an instruction of its own
+SSD float opaque(float x) { SS_REG(x); return x; }
+SSD void ref_fma(ssf2 a, float f, ssf2 c, float* o) {
+  o[0] = __builtin_fmaf(opaque(a.x), opaque(f), opaque(c.x));
+  o[1] = __builtin_fmaf(opaque(a.y), opaque(f), opaque(c.y));
+}
+SSD void ref_mul(ssf2 a, float f, float* o) {
+  o[0] = opaque(a.x) * opaque(f);
+  o[1] = opaque(a.y) * opaque(f);
+}
+SSD void put2(float* o, ssf2 v) { o[0] = v.x; o[1] = v.y; }
+
+SSD void run_pk(const float* in, float* out) {
+  const ssf2 a = pkv(in[0], in[1]), s = pkv(in[2], in[3]), c = pkv(in[4], in[5]);
+  put2(out + 0, pk_fma_half<0>(a, s, c));
+  put2(out + 2, pk_fma_half<1>(a, s, c));
+  put2(out + 4, pk_fma_half<0>(a, a, c));
+  put2(out + 6, pk_fma_half<1>(a, a, c));
+  put2(out + 8, pk_mul_half<0>(a, s));
+  put2(out + 10, pk_mul_half<1>(a, s));
+  put2(out + 12, pk_mul_half<0>(a, a));
+  put2(out + 14, pk_mul_half<1>(a, a));
+  ref_fma(a, s.x, c, out + 16);
+  ref_fma(a, s.y, c, out + 18);
+  ref_fma(a, a.x, c, out + 20);
+  ref_fma(a, a.y, c, out + 22);
+  ref_mul(a, s.x, out + 24);
+  ref_mul(a, s.y, out + 26);
+  ref_mul(a, a.x, out + 28);
+  ref_mul(a, a.y, out + 30);
+}
+
+// the joint-limit and joint-torque forms as the step kernels had them before joint_limit (ss_dynamics.hpp): the reference of
+// tests/test_limit_forms.py, kept VERBATIM
+template <class Model, int j>
+SSD void joint_tau_old(float power, float q, float qd, float act, float& viol_o, float& kl_o, float& dl_o, float& tau, float& Dadd) {
+  constexpr float h = kH;
+  constexpr float lo = Model::lo[j], hi = Model::hi[j], kd = Model::damping[j], ks = Model::stiffness[j];
+  constexpr float klim = Model::klim[j], dlim = Model::dlim[j], arm = Model::armature[j], tq = Model::torque[j];
+  float viol = q > hi ? q - hi : (q < lo ? q - lo : 0.f);
+  bool lim = viol != 0.f;
+  float kl = lim ? klim : 0.f, dl = lim ? dlim : 0.f;
+  tau = power * tq * act - kd * qd - ks * (q + h * qd) - kl * (viol + h * qd) - dl * qd;
+  Dadd = arm + h * (kd + dl) + (h * h) * (ks + kl);
+  viol_o = viol; kl_o = kl; dl_o = dl;
+}
+
+template <class Model>
+SSD void run_limit(const float* in, float* out) {
+  const float power = in[0], act = in[1];
+  static_for<0, NJ>([&](auto Jc) {
+    constexpr int j = decltype(Jc)::value;
+    const float q = in[2 + 2 * j], qd = in[3 + 2 * j];
+    float* o = out + 10 * j;
+    joint_limit<Model, j>(q, o[0], o[1], o[2]);
+    joint_tau<Model, j>(power, q, qd, act, o[3], o[4]);
+    joint_tau_old<Model, j>(power, q, qd, act, o[5], o[6], o[7], o[8], o[9]);
+  });
+}
+
+template <class Model>
+SSD void run_tau(const float* in, float* out) {
+  const float power = in[0], actl = in[1], acta = in[2];
+  static_for<0, 4>([&](auto Ic) {
+    constexpr int i = decltype(Ic)::value, jl = 3 + i, ja = 13 + i;
+    const float ql = in[3 + 2 * jl], qdl = in[4 + 2 * jl], qa = in[3 + 2 * ja], qda = in[4 + 2 * ja];
+    float* o = out + 8 * i;
+    ssf2 tau2, dadd2;
+    joint_tau<Model, jl, ja>(power, pkv(ql, qa), pkv(qdl, qda), pkv(actl, acta), tau2, dadd2);
+    o[0] = tau2.x; o[1] = tau2.y; o[2] = dadd2.x; o[3] = dadd2.y;
+    joint_tau<Model, jl>(power, ql, qdl, actl, o[4], o[6]);
+    joint_tau<Model, ja>(power, qa, qda, acta, o[5], o[7]);
+  });
+}
 
 template <class Model, int OP>
 SSD void run_case(const float* p, float* o, const Lds& L) {
@@ -776,6 +872,12 @@ SSD void run_case(const float* p, float* o, const Lds& L) {
     o[0] = (float)fr.contact; o[1] = (float)fr.on_target;
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[2 + i] = fr.sole[i];
+  } else if constexpr (OP == OP_PK_HALF) {
+    run_pk(p, o);
+  } else if constexpr (OP == OP_LIMIT_FORMS) {
+    run_limit<Model>(p, o);
+  } else if constexpr (OP == OP_TAU_PAIR) {
+    run_tau<Model>(p, o);
   }
 }
 

@@ -1,7 +1,7 @@
 // host_harness.cpp -- compiles the SAME kernel source (steppingstone_amd/csrc/*.hpp) for the CPU so that the
 // per-lane device code can be checked against the oracle in the GPU-less build container (pre-flight / debugging).
 // TEST INFRASTRUCTURE ONLY: it is built by tests/host_lib.py into tests/host/, never shipped, and the product
-// library contains no host path.  Build: hipcc --cuda-host-only -x hip ... (see tests/host_lib.py).
+// library contains no host path.  Build: hipcc, host pass only, -x hip ... (see tests/host_lib.py, tests/native_build.py).
 #include <hip/hip_runtime.h>
 
 #include <atomic>

@@ -1,28 +1,23 @@
-"""Builds and binds tests/host/host_harness.cpp: the product's kernel source compiled for the CPU (hipcc
---cuda-host-only).  TEST INFRASTRUCTURE for the GPU-less container; never imported by steppingstone_amd."""
+"""Builds and binds tests/host/host_harness.cpp: the product's kernel source compiled for the CPU (the recipe of
+native_build.py).  TEST INFRASTRUCTURE for the GPU-less container; never imported by steppingstone_amd."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host")
+import native_build
+from native_build import HOST_DIR
+
 LIB = os.path.join(HOST_DIR, "libss_host.so")
 SRC = os.path.join(HOST_DIR, "host_harness.cpp")
-CSRC = os.path.join(ROOT, "steppingstone_amd", "csrc")
 
 INFO_DTYPE = np.dtype([("ep_ret", "f4"), ("ep_len", "f4"), ("bad_transition", "i4"), ("steps_reached", "i4"),
                        ("update_terrain", "i4"), ("ep_ret_lo", "f4")])
 
 
 def build():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    subprocess.check_call(["hipcc", "--cuda-host-only", "-x", "hip", "-O1", "-std=c++17", "-fPIC", "-shared",
-                           "-fno-signed-zeros", "-fno-math-errno", "-DSS_HOST_HARNESS", "-pthread", SRC, "-o", LIB], stderr=subprocess.DEVNULL)
-    return LIB
+    # no -ffp-contract=on here, unlike the probe: the host parity tests were measured with the harness built this way
+    return native_build.build_host(SRC, LIB, ["-pthread"])
 
 
 _lib = None

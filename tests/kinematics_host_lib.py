@@ -1,25 +1,20 @@
 """Builds and binds tests/host/kinematics_host.cpp: the kinematic readout's code (steppingstone_amd/csrc/ss_kinematics.hpp) compiled for
-the CPU (hipcc --cuda-host-only, the recipe of render_host_lib.py).  TEST INFRASTRUCTURE for the GPU-less container; never imported by
+the CPU (the recipe of native_build.py).  TEST INFRASTRUCTURE for the GPU-less container; never imported by
 steppingstone_amd."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from render_host_lib import CSRC, HOST_DIR, INCLUDE, hipcc
+import native_build
+from native_build import HOST_DIR
 
 LIB = os.path.join(HOST_DIR, "libkinematics_host.so")
 SRC = os.path.join(HOST_DIR, "kinematics_host.cpp")
 
 
 def build():
-    deps = [SRC, INCLUDE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    subprocess.check_call([hipcc(), "--cuda-host-only", "-x", "hip", "-O1", "-std=c++17", "-fPIC", "-shared", "-fno-signed-zeros",
-                           "-fno-math-errno", "-DSS_HOST_HARNESS", SRC, "-o", LIB])
-    return LIB
+    return native_build.build_host(SRC, LIB)
 
 
 _lib = None

@@ -1,46 +1,37 @@
-"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas and one whole substep
-behind one C entry, one operator per call.
-    host flavour:   compiled here for the CPU (hipcc --cuda-host-only) into tests/host/libss_probe_host.so, numpy pointers;
+"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas, one whole substep and
+the forms that must agree bitwise with the ones they replaced, behind one C entry, one operator per call.
+    host flavour:   compiled here for the CPU (the recipe of native_build.py) into tests/host/libss_probe_host.so, numpy pointers;
     device flavour: steppingstone_amd/lib/libss_probe.so, built for gfx950 by steppingstone_amd.build.build_probe(), torch tensors.
 TEST INFRASTRUCTURE; never imported by steppingstone_amd."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host")
+import native_build
+from native_build import HOST_DIR, ROOT, hipcc  # noqa: F401  (re-exported: the tests ask this module for ROOT and hipcc())
+
 HOST_LIB = os.path.join(HOST_DIR, "libss_probe_host.so")
 SRC = os.path.join(ROOT, "tests", "device", "ss_probe.hip")
-CSRC = os.path.join(ROOT, "steppingstone_amd", "csrc")
 
 # the op numbers of ss_probe.hip's enum, in its order
 OPS = ["rot", "rot2", "cross_r", "cross_rP", "xmotion", "xforce", "xmotionP", "xforceP", "xinertia", "xinertiaP", "abi_body",
        "abi_add_bodyP", "body_bias", "body_biasP", "imp_up", "imp_down", "imp_down_pair", "imp_up_pair", "imp_down_pair_loaded",
        "aba_acc", "aba_accP", "quat_rot", "mirror_sv", "abi_dense", "pack", "sincos", "chol", "xchg", "philox",
-       "fk_detect", "jacobian_rows", "contact_ops", "sampler", "window_prob", "obs_terms", "substep"]
+       "fk_detect", "jacobian_rows", "contact_ops", "sampler", "window_prob", "obs_terms", "substep",
+       "pk_half", "limit_forms", "tau_pair"]
 OP = {name: i for i, name in enumerate(OPS)}
 UNSUPPORTED = -2
 
 
-def hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
-def host_ready(src=SRC, lib=HOST_LIB, csrc=CSRC):
+def host_ready():
     """the host build exists and is newer than its sources"""
-    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    return os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps)
+    return native_build.host_ready(SRC, HOST_LIB)
 
 
-def build_host(src=SRC, lib=HOST_LIB, csrc=CSRC):
-    if host_ready(src, lib, csrc):
-        return lib
-    subprocess.check_call([hipcc(), "--cuda-host-only", "-x", "hip", "-O1", "-std=c++17", "-fno-signed-zeros", "-ffp-contract=on",
-                           "-fPIC", "-shared", "-pthread", "-fno-math-errno", "-DSS_HOST_HARNESS", "-DSS_PROBE_HOST", src, "-o", lib])
-    return lib
+def build_host():
+    # -ffp-contract=on as in the product's FLAGS: the probe's operators fuse on the CPU where they fuse on the GPU
+    return native_build.build_host(SRC, HOST_LIB, ["-ffp-contract=on", "-pthread", "-DSS_PROBE_HOST"])
 
 
 def _bind(path):

@@ -1,18 +1,15 @@
 """Builds and binds tests/host/render_host.cpp: the render kernels' code (steppingstone_amd/csrc/ss_render.hpp) compiled for the CPU
-(hipcc --cuda-host-only).  TEST INFRASTRUCTURE for the GPU-less container; never imported by steppingstone_amd."""
+(the recipe of native_build.py).  TEST INFRASTRUCTURE for the GPU-less container; never imported by steppingstone_amd."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "tests", "host")
+import native_build
+from native_build import HOST_DIR, hipcc  # noqa: F401  (hipcc re-exported: the tests ask this module for it)
+
 LIB = os.path.join(HOST_DIR, "librender_host.so")
 SRC = os.path.join(HOST_DIR, "render_host.cpp")
-CSRC = os.path.join(ROOT, "steppingstone_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include", "steppingstone.h")
 
 
 class Camera(C.Structure):
@@ -20,17 +17,8 @@ class Camera(C.Structure):
                 ("far_m", C.c_float), ("flags", C.c_int32)]
 
 
-def hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 def build():
-    deps = [SRC, INCLUDE] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    subprocess.check_call([hipcc(), "--cuda-host-only", "-x", "hip", "-O1", "-std=c++17", "-fPIC", "-shared", "-fno-signed-zeros",
-                           "-fno-math-errno", "-DSS_HOST_HARNESS", SRC, "-o", LIB])
-    return LIB
+    return native_build.build_host(SRC, LIB)
 
 
 _lib = None

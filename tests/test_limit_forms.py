@@ -1,6 +1,6 @@
 """The joint-limit forms of ss_dynamics.hpp -- viol = min(q - lo, 0) + max(q - hi, 0) and the limit gains as K's bits under an
 all-or-nothing mask (joint_limit) -- and the joint torque / implicit diagonal built on them (joint_tau) must be the forms they
-replaced, BITWISE, for every joint of both robots.  The replaced forms are kept verbatim in tests/device/ss_probe_pk.hip, which
+replaced, BITWISE, for every joint of both robots.  The replaced forms are kept verbatim in tests/device/ss_probe.hip, which
 evaluates both sides per case, one lane per case.
 
 Grid per joint, q: both bounds, nextafter on either side of each, the bounds +- the smallest and the largest denormal, far outside
@@ -13,7 +13,7 @@ import re
 import numpy as np
 import pytest
 
-import probe_pk_lib
+import probe_lib
 
 NJ = 21
 COLS = ["viol", "kl", "dl", "tau", "Dadd"]
@@ -22,7 +22,7 @@ N_RANDOM = 4096
 
 def bounds():
     """(lo, hi)[kind][21] as ss_model_tables.hpp states them"""
-    text = open(os.path.join(probe_pk_lib.ROOT, "steppingstone_amd", "csrc", "ss_model_tables.hpp")).read()
+    text = open(os.path.join(probe_lib.ROOT, "steppingstone_amd", "csrc", "ss_model_tables.hpp")).read()
     out = []
     for name in ("lo", "hi"):
         rows = re.findall(r"static constexpr float %s\[21\] = \{([^}]*)\}" % name, text)
@@ -70,7 +70,7 @@ def grid(kind):
 def check(flavour, kind):
     x = grid(kind)
     assert 4000 < x.shape[0] < 5000
-    out = probe_pk_lib.run(flavour, "limit", kind, x).reshape(x.shape[0], NJ, 2, 5)
+    out = probe_lib.run(flavour, "limit_forms", kind, x).reshape(x.shape[0], NJ, 2, 5)
     new, old = out[:, :, 0, :], out[:, :, 1, :]
     same = (new.view(np.uint32) == old.view(np.uint32)) | ((new == 0) & (old == 0))
     if not same.all():
@@ -85,7 +85,7 @@ def check(flavour, kind):
 
 @pytest.mark.parametrize("kind", [0, 1], ids=["walker3d", "mike"])
 def test_limit_forms_host(kind):
-    if not probe_pk_lib.hipcc():
+    if not probe_lib.hipcc():
         pytest.skip("no hipcc: the host build of the probe cannot be made")
     check("host", kind)
 

@@ -2,7 +2,7 @@
 half of a pair, picked by the instruction itself) must be two scalar fmaf / two products of the same operands, bitwise, for both
 halves -- on the device (inline assembly for the high half) and in the host build of the same header (plain fmaf).
 
-16384 cases = one launch of 256 wavefronts' 64 lanes, through tests/device/ss_probe_pk.hip, which evaluates each form and, beside it,
+16384 cases = one launch of 256 wavefronts' 64 lanes, through tests/device/ss_probe.hip, which evaluates each form and, beside it,
 the scalar reference with every operand made opaque.  The operands are drawn from: +-0, the smallest and the largest denormal of
 either sign, +-inf, quiet and signalling NaN payloads, +-1, 1 + 2^-23, the largest and the smallest normal, triples whose product
 rounds differently fused and unfused, and random values over 60 binades.  Every case is also evaluated with ONE register as pair and
@@ -13,7 +13,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import probe_pk_lib
+import probe_lib
 
 N = 64 * 256
 NAMES = ["fma<0>(a,s,c)", "fma<1>(a,s,c)", "fma<0>(a,a,c)", "fma<1>(a,a,c)", "mul<0>(a,s)", "mul<1>(a,s)", "mul<0>(a,a)", "mul<1>(a,a)"]
@@ -79,7 +79,7 @@ def exact_reference(x):
 
 def check(flavour):
     x = cases()
-    out = probe_pk_lib.run(flavour, "pk", 0, x)
+    out = probe_lib.run(flavour, "pk_half", 0, x)
     got, ref = out[:, :16].view(np.uint32), out[:, 16:].view(np.uint32)
     # Bits, NaN payloads included -- with ONE exception: where BOTH factors of an output's product are NaN (the half of a and the
     # broadcast factor), which payload comes out depends on which of the two the instruction takes as its first operand, and a
@@ -107,7 +107,7 @@ def check(flavour):
 
 
 def test_host_fallback_is_two_fmaf():
-    if not probe_pk_lib.hipcc():
+    if not probe_lib.hipcc():
         pytest.skip("no hipcc: the host build of the probe cannot be made")
     check("host")
 

@@ -1,6 +1,6 @@
 """joint_tau's pair overload (ss_dynamics.hpp) -- the explicit joint torque and the implicit diagonal of a {leg, arm} pair of joints on
 packed instructions, as the three-helper step kernels compute them for joints (3,13) (4,14) (5,15) (6,16) -- must be joint_tau per
-joint, BITWISE, for both robots.  tests/device/ss_probe_pair.hip evaluates both sides per case, one lane per case, one launch per robot.
+joint, BITWISE, for both robots.  tests/device/ss_probe.hip evaluates both sides per case, one lane per case, one launch per robot.
 
 Inputs: the grid of tests/test_limit_forms.py (both sides of both limits, at the limits, +-0, +-inf, NaN, denormals in q and qd, about 4100
 cases per joint) with power 1.0 and 0.6 and actions that take +-0, +-1, +-inf, NaN and denormals as well, drawn apart for the two halves.
@@ -14,7 +14,7 @@ the other sign than imp_down's), so there is nothing of it to test."""
 import numpy as np
 import pytest
 
-import probe_pair_lib
+import probe_lib
 import test_limit_forms as lf
 
 LEG, ARM = [3, 4, 5, 6], [13, 14, 15, 16]
@@ -48,7 +48,7 @@ def tau_rows(kind):
 def check_tau(flavour, kind):
     x = tau_rows(kind)
     assert 4000 < x.shape[0] < 5000
-    out = probe_pair_lib.run(flavour, "tau", kind, x).reshape(x.shape[0], 4, 2, 4)
+    out = probe_lib.run(flavour, "tau_pair", kind, x).reshape(x.shape[0], 4, 2, 4)
     new, old = out[:, :, 0], out[:, :, 1]
     same = same_bits(new, old)
     zero_sign = ~same & (new == 0) & (old == 0)
@@ -66,7 +66,7 @@ def check_tau(flavour, kind):
 
 @pytest.mark.parametrize("kind", [0, 1], ids=["walker3d", "mike"])
 def test_pair_tau_host(kind):
-    if not probe_pair_lib.hipcc():
+    if not probe_lib.hipcc():
         pytest.skip("no hipcc: the host build of the probe cannot be made")
     check_tau("host", kind)
 
