@@ -39,7 +39,7 @@ extern "C" {
                             * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) and the per-env
                             * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
                             * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
-                            * readout (ss_kinematics). */
+                            * readout (ss_kinematics) and the force readout (ss_step_forces). */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -245,6 +245,31 @@ int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int
 #define SS_KIN_SUMMARY 12
 #define SS_KIN_CORNER 8
 int ss_kinematics(ss_env* env, const int32_t* env_ids, int32_t m, float* body_twist, float* summary, float* corners, void* stream);
+
+/* Force readout: a DRY RUN of one control step of the m envs listed in env_ids under the actions act (docs/PHYSICS.md "Force readout"
+ * has the definitions); added under version 4 (nothing existing moved).  It runs the four substeps of ss_step on a copy of the state
+ * and reports what they do; it only READS the environment state (no state word, terrain row or RNG counter changes), is ordered on
+ * `stream`, never synchronises the host and allocates nothing.  No reward, termination, target logic or reset is evaluated.
+ * env_ids: DEVICE [m] int32 with the conventions of ss_kinematics (NULL: envs 0..m-1, needs m == N; m == 0 does nothing; an id outside
+ * [0, N) is skipped: no row of it is read or written).  act: DEVICE [m, 21], row k is the action for env env_ids[k], policy coordinates,
+ * clipped as in ss_step.  Outputs are DEVICE pointers, 16-byte aligned, f32; any may be NULL, not all three when m > 0.  Bad host
+ * arguments return SS_ERR_INVALID and launch nothing.  A row's bits depend on the env's state, the knobs (ss_set_power) and its action
+ * row alone: not on N, m, k, repeated ids or the outputs asked for.
+ *   contacts [m, SS_FRC_SUBSTEPS, 8, SS_FRC_CONTACT]: substep s, sole corner c = 4 * foot + corner (the order of ss_kinematics):
+ *     0 carrier slot as a float (0, 1, 2: stone n-1, n, n+1; -1: none; the coding of ss_kinematics corners word 7), the detection at
+ *     the START of substep s | 1 penetration in metres | 2:5 contact force over the substep, lambda / h along n, t1, t2 of PHYSICS.md
+ *     3.4, in newtons | 5:8 the same force as a world vector.  A corner that is not carried has words 1:8 exactly 0.
+ *   joints [m, SS_FRC_SUBSTEPS, SS_FRC_JOINT, 21], joint order and +axis convention of ss_get_state: row 0 q, row 1 qd at the start
+ *     of substep s | row 2 the explicit torque tau_j of PHYSICS.md 3.1 | row 3 the torque the joint applied over the substep under the
+ *     linearly-implicit scheme, tau_j - (Dadd_j - armature_j) (qd+_j - qd_j) / h.
+ *   next_state [m, SS_FRC_STATE]: words 0:55 of the ss_get_state layout after the four substeps | 55 flags as a float: bit 0 / 1 right /
+ *     left foot contact, bit 2 / 3 right / left foot touches the target stone, both of the last substep's detection. */
+#define SS_FRC_SUBSTEPS 4
+#define SS_FRC_CONTACT 8   /* words per corner row */
+#define SS_FRC_JOINT 4     /* rows per substep */
+#define SS_FRC_STATE 56
+int ss_step_forces(ss_env* env, const int32_t* env_ids, int32_t m, const float* act,
+                   float* contacts, float* joints, float* next_state, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

@@ -21,6 +21,9 @@ hipError_t launch_body_poses(const Params& P, int kind, float* out, hipStream_t 
 // compiled in ss_kinematics.hip (the kinematic readout, docs/PHYSICS.md)
 hipError_t launch_kinematics(const Params& P, int kind, const int32_t* env_ids, int m, float* body_twist, float* summary, float* corners,
                              hipStream_t st);
+// compiled in ss_forces.hip (the force readout, docs/PHYSICS.md)
+hipError_t launch_step_forces(const Params& P, int kind, const int32_t* env_ids, int m, const float* act, float* contacts, float* joints,
+                              float* next_state, hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -775,6 +778,21 @@ int ss_kinematics(ss_env* env, const int32_t* env_ids, int32_t m, float* body_tw
     return fail(SS_ERR_INVALID, "ss_kinematics: body_twist, summary and corners must be 16-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_kinematics(env->P, env->kind, env_ids, m, body_twist, summary, corners, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_step_forces(ss_env* env, const int32_t* env_ids, int32_t m, const float* act, float* contacts, float* joints, float* next_state,
+                   void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_step_forces: m must be >= 0");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_step_forces: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (!act) return fail(SS_ERR_INVALID, "ss_step_forces: act is NULL");
+  if (!contacts && !joints && !next_state) return fail(SS_ERR_INVALID, "ss_step_forces: contacts, joints and next_state are all NULL");
+  if (((uintptr_t)contacts | (uintptr_t)joints | (uintptr_t)next_state) & 15)
+    return fail(SS_ERR_INVALID, "ss_step_forces: contacts, joints and next_state must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_step_forces(env->P, env->kind, env_ids, m, act, contacts, joints, next_state, (hipStream_t)stream));
   return SS_OK;
 }
 

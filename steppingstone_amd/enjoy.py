@@ -10,7 +10,12 @@ with PIL when it is importable; otherwise, and for --out *.npy, the frames are s
 --trace FILE.npz also writes what the frames show as numbers (SteppingStoneVecEnv.kinematics, docs/PHYSICS.md 9), one entry per control
 step and env, for the state each step ends in: com [T,K,3], com_vel [T,K,3], corner_height [T,K,8] (sole corners over the target stone's
 surface plane), corner_carrier [T,K,8] (the stone slot that carries each corner, -1: none), contact [T,K,2] (the observation's foot
-contact flags, right / left), next_step_index [T,K], done [T,K]."""
+contact flags, right / left), next_step_index [T,K], done [T,K].
+
+--forces (only together with --trace) adds the force readout of every step (SteppingStoneVecEnv.step_forces, docs/PHYSICS.md 10), taken
+as a dry run from the state the step STARTS in, with the action the policy chose: contact_force [T,K,4,8,8] (per substep and sole
+corner: carrier slot, penetration, force along n / t1 / t2, force as a world vector) and joint_torque [T,K,4,21] (the torque every joint
+applied over each substep)."""
 import argparse
 import math
 import os
@@ -51,12 +56,15 @@ def tile(frames):
 
 
 TRACE_KEYS = ("com", "com_vel", "corner_height", "corner_carrier")
+FORCE_KEYS = ("contact_force", "joint_torque")
 
 
 def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240), camera="track", device="cuda:0", out=None,
-        log=print, trace=None):
+        log=print, trace=None, forces=False):
     """Roll the policy out deterministically; returns the [T, H, W, 3] uint8 animation (and writes it to `out` if given; the kinematic
     trace of the module docstring to `trace` if given)."""
+    if forces and not trace:
+        raise ValueError("forces=True needs a trace file to write to")
     ac = load_policy(net, device)
     ac.eval()
     env = SteppingStoneVecEnv(env_id, envs, seed=seed, device=device, return_numpy=False)
@@ -66,7 +74,7 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
     log("Env: {}".format(env_id))
     log("Model: {}".format(os.path.basename(net)))
     frames = []
-    rec = {k: [] for k in TRACE_KEYS + ("contact", "next_step_index", "done")}
+    rec = {k: [] for k in TRACE_KEYS + ("contact", "next_step_index", "done") + (FORCE_KEYS if forces else ())}
     try:
         obs = env.reset()
         ep_reward = torch.zeros(envs, dtype=torch.float64, device=env.device)
@@ -74,6 +82,12 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
             frames.append(tile(env.render("rgb_array", width=W, height=H, camera=cam).cpu().numpy()))
             with torch.no_grad():
                 _, action, _ = ac.act(obs, deterministic=True)
+            if forces:                     # before the step: a dry run of it from the current state
+                dry = env.step_forces(action, next_state=False)
+                as_np = lambda k: dry[k].cpu().numpy()
+                rec["contact_force"].append(np.concatenate([as_np("contact_slot")[..., None].astype(np.float32), as_np("contact_pen")[..., None],
+                                                            as_np("contact_force"), as_np("contact_force_world")], -1))
+                rec["joint_torque"].append(as_np("joint_torque"))
             obs, rew, done, _ = env.step(action)
             ep_reward += rew.double()
             if trace:
@@ -132,9 +146,12 @@ def main(argv=None):
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--out", default="enjoy.gif", help=".gif (needs PIL) or .npy")
     p.add_argument("--trace", default=None, metavar="FILE.npz", help="also write COM, sole-corner heights / carriers, contact flags per step")
+    p.add_argument("--forces", action="store_true", help="with --trace: also write contact forces and applied joint torques per substep")
     a = p.parse_args(argv)
+    if a.forces and not a.trace:
+        p.error("--forces needs --trace")
     w, h = (int(x) for x in a.size.lower().split("x"))
-    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out, trace=a.trace)
+    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out, trace=a.trace, forces=a.forces)
     return 0
 
 

@@ -173,6 +173,13 @@ class HipBackend:
         opt = lambda t: _ptr(t) if t is not None else None
         _lib.check(self.lib.ss_kinematics(self.h, opt(env_ids), int(m), opt(body_twist), opt(summary), opt(corners), _stream(self.device)))
 
+    def step_forces(self, env_ids, m, act, contacts, joints, next_state):
+        """env_ids: int32 device tensor [m], or None for envs 0..m-1 (m == N); act [m,21]; contacts [m,4,8,8] / joints [m,4,4,21] /
+        next_state [m,56]: float32 device tensors or None, not all three (docs/PHYSICS.md 10)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_step_forces(self.h, opt(env_ids), int(m), _ptr(act), opt(contacts), opt(joints), opt(next_state),
+                                           _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
@@ -496,6 +503,50 @@ class SteppingStoneVecEnv:
                        corner_carrier=co[:, :, 7].to(torch.int32))
         return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
 
+    def step_forces(self, actions, env_ids=None, contacts=True, joints=True, next_state=True):
+        """Dry run of one control step of the envs env_ids names (default: all; the forms of get_state()) under `actions` ([m,21], row k
+        for env env_ids[k]; [N,21] without env_ids; policy coordinates, clipped as in step()): what the four substeps would do, read on
+        the GPU from the current state, which stays as it is (docs/PHYSICS.md 10).  Returns a dict of tensors on the env's device
+        (numpy arrays in numpy mode), m rows in env_ids order, holding the groups asked for:
+          contacts:   contact_slot [m,4,8] int32 (per substep and sole corner 4 * foot + k, foot 0 = right: carried by stone n-1 / n / n+1 =
+                      0 / 1 / 2 at the substep's start, -1: by none), contact_pen [m,4,8] (metres), contact_force [m,4,8,3] (newtons along
+                      n, t1, t2), contact_force_world [m,4,8,3];
+          joints:     joint_q, joint_qd [m,4,21] (start of each substep), joint_tau [m,4,21] (explicit torque), joint_torque [m,4,21] (the
+                      torque applied over the substep under the linearly-implicit scheme);
+          next_state: next_state [m,55] (words 0:55 of get_state() after the step), next_contact [m,2] bool (right / left foot),
+                      next_on_target [m,2] bool."""
+        if not hasattr(self.backend, "step_forces"):
+            raise NotImplementedError("this backend has no force readout")
+        if not (contacts or joints or next_state):
+            raise ValueError("step_forces: ask for at least one of contacts, joints, next_state")
+        if env_ids is None:
+            ids, m = None, self.num_envs
+        else:
+            _, host_ids = self._env_ids(env_ids, allow_mask=False)
+            m = int(host_ids.size)
+            ids = torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        act = torch.as_tensor(actions, dtype=torch.float32).to(self.device).contiguous()
+        if act.numel() != m * ACT_DIM:
+            raise ValueError("step_forces: %d envs need actions of shape (%d, %d), got %s" % (m, m, ACT_DIM, tuple(act.shape)))
+        act = act.reshape(m, ACT_DIM)
+        new = lambda *shape: torch.empty((m,) + shape, dtype=torch.float32, device=self.device)
+        co = new(_lib.FRC_SUBSTEPS, _lib.KIN_CORNER, _lib.FRC_CONTACT) if contacts else None
+        jo = new(_lib.FRC_SUBSTEPS, _lib.FRC_JOINT, ACT_DIM) if joints else None
+        ns = new(_lib.FRC_STATE) if next_state else None
+        if m:
+            self.backend.step_forces(ids, m, act, co, jo, ns)
+        out = {}
+        if contacts:
+            out.update(contact_slot=co[..., 0].to(torch.int32), contact_pen=co[..., 1], contact_force=co[..., 2:5],
+                       contact_force_world=co[..., 5:8])
+        if joints:
+            out.update(joint_q=jo[:, :, 0], joint_qd=jo[:, :, 1], joint_tau=jo[:, :, 2], joint_torque=jo[:, :, 3])
+        if next_state:
+            flags = ns[:, _lib.FRC_STATE - 1].to(torch.int32)
+            out.update(next_state=ns[:, :_lib.FRC_STATE - 1], next_contact=torch.stack([flags & 1, (flags >> 1) & 1], 1).bool(),
+                       next_on_target=torch.stack([(flags >> 2) & 1, (flags >> 3) & 1], 1).bool())
+        return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
+
     @property
     def unwrapped(self):
         return self
@@ -720,6 +771,11 @@ class SteppingStoneEnv:
         self.robot.feet_contact[:] = obs[0, 48:50]
         info = dict(infos[0])
         return obs[0], float(rew[0]), bool(done[0]), info
+
+    def step_forces(self, action):
+        """Dry run of step(action) from the current state (SteppingStoneVecEnv.step_forces): the dict without the env axis."""
+        out = self.vec.step_forces(np.asarray(action, np.float32).reshape(1, ACT_DIM))
+        return {k: v[0] for k, v in out.items()}
 
     def render(self, mode="rgb_array", width=256, height=192, camera=None):
         """One (H, W, 3) uint8 frame of the env (SteppingStoneVecEnv.render); mode="human" raises NotImplementedError."""
