@@ -39,7 +39,8 @@ extern "C" {
                             * The rendering entry points (ss_camera, ss_camera_default, ss_body_poses, ss_render) and the per-env
                             * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
                             * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
-                            * readout (ss_kinematics) and the force readout (ss_step_forces). */
+                            * readout (ss_kinematics), the force readout (ss_step_forces) and the equation-of-motion readout
+                            * (ss_eom). */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -270,6 +271,27 @@ int ss_kinematics(ss_env* env, const int32_t* env_ids, int32_t m, float* body_tw
 #define SS_FRC_STATE 56
 int ss_step_forces(ss_env* env, const int32_t* env_ids, int32_t m, const float* act,
                    float* contacts, float* joints, float* next_state, void* stream);
+
+/* Equation-of-motion readout of the m envs listed in env_ids (docs/PHYSICS.md "Equation of motion readout" has the definitions); added
+ * under version 4 (nothing existing moved).  It only READS the environment state, is ordered on `stream`, never synchronises the host
+ * and allocates nothing.  env_ids: DEVICE [m] int32 with the conventions of ss_kinematics (NULL: envs 0..m-1, needs m == N; m == 0 does
+ * nothing; an id outside [0, N) is skipped: no row of it is read or written).  Outputs are DEVICE pointers, 16-byte aligned, f32; any
+ * may be NULL, not all three when m > 0.  Bad host arguments return SS_ERR_INVALID and launch nothing.  A row's bits depend on the env's
+ * state alone: not on N, m, k, repeated ids or the outputs asked for.
+ * Generalised velocity nu = [w_b (3); v_b (3); qd (21)] = state words 7:13 | 34:55: the base twist in body coordinates, the joints in the
+ * order and about the +axis of ss_get_state.  DoF i < 6 is the base, DoF 6 + j is joint j.
+ *   mass [m, SS_EOM_DOF, SS_EOM_DOF]: joint-space inertia M(q) = H(q) + diag(0_6, armature): the composite-rigid-body matrix of the 22
+ *     bodies plus the rotor armature of PHYSICS.md 3.1 on the joint diagonal.  Both triangles are written, M == M^T bit for bit.
+ *   forces [m, SS_EOM_FORCES, SS_EOM_DOF]: row 0 c(q, nu), the velocity-product (Coriolis / centrifugal) generalised force: inverse
+ *     dynamics at zero acceleration without gravity, base rows included | row 1 g(q) = M[:, 3:6] R^T (0, 0, -9.8), the generalised
+ *     force of gravity | row 2 passive: [0_6; -damping qd - stiffness q - kl viol - dl qd], the joints' springs, dampers and limits in
+ *     continuous time (PHYSICS.md 3.1's tau_j at h = 0 and tau_m = 0).
+ *   corner_jac [m, SS_KIN_CORNER, 3, SS_EOM_DOF]: J_c with x_c-dot = J_c nu the world velocity of sole corner c = 4 * foot + corner (the
+ *     order of ss_kinematics), carried or not.
+ * Together: M nu-dot + c = g + [0; tau_m + passive] + sum_c J_c^T f_c, f_c the world contact force on corner c. */
+#define SS_EOM_DOF 27      /* 6 base + 21 joints */
+#define SS_EOM_FORCES 3    /* rows of `forces` */
+int ss_eom(ss_env* env, const int32_t* env_ids, int32_t m, float* mass, float* forces, float* corner_jac, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

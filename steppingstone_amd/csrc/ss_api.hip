@@ -24,6 +24,9 @@ hipError_t launch_kinematics(const Params& P, int kind, const int32_t* env_ids, 
 // compiled in ss_forces.hip (the force readout, docs/PHYSICS.md)
 hipError_t launch_step_forces(const Params& P, int kind, const int32_t* env_ids, int m, const float* act, float* contacts, float* joints,
                               float* next_state, hipStream_t st);
+// compiled in ss_eom.hip (the equation-of-motion readout, docs/PHYSICS.md)
+hipError_t launch_eom(const Params& P, int kind, const int32_t* env_ids, int m, float* mass, float* forces, float* corner_jac,
+                      hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -793,6 +796,19 @@ int ss_step_forces(ss_env* env, const int32_t* env_ids, int32_t m, const float* 
     return fail(SS_ERR_INVALID, "ss_step_forces: contacts, joints and next_state must be 16-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_step_forces(env->P, env->kind, env_ids, m, act, contacts, joints, next_state, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_eom(ss_env* env, const int32_t* env_ids, int32_t m, float* mass, float* forces, float* corner_jac, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_eom: m must be >= 0");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_eom: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (!mass && !forces && !corner_jac) return fail(SS_ERR_INVALID, "ss_eom: mass, forces and corner_jac are all NULL");
+  if (((uintptr_t)mass | (uintptr_t)forces | (uintptr_t)corner_jac) & 15)
+    return fail(SS_ERR_INVALID, "ss_eom: mass, forces and corner_jac must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_eom(env->P, env->kind, env_ids, m, mass, forces, corner_jac, (hipStream_t)stream));
   return SS_OK;
 }
 

@@ -180,6 +180,12 @@ class HipBackend:
         _lib.check(self.lib.ss_step_forces(self.h, opt(env_ids), int(m), _ptr(act), opt(contacts), opt(joints), opt(next_state),
                                            _stream(self.device)))
 
+    def eom(self, env_ids, m, mass, forces, corner_jac):
+        """env_ids: int32 device tensor [m], or None for envs 0..m-1 (m == N); mass [m,27,27] / forces [m,3,27] / corner_jac [m,8,3,27]:
+        float32 device tensors or None, not all three (docs/PHYSICS.md 11)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_eom(self.h, opt(env_ids), int(m), opt(mass), opt(forces), opt(corner_jac), _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
@@ -547,6 +553,41 @@ class SteppingStoneVecEnv:
                        next_on_target=torch.stack([(flags >> 2) & 1, (flags >> 3) & 1], 1).bool())
         return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
 
+    def equation_of_motion(self, env_ids=None, mass=True, forces=True, jacobians=True):
+        """The terms of the equation of motion of the envs env_ids names (default: all; the forms of get_state()), read on the GPU from
+        the current state (docs/PHYSICS.md 11):  M nu-dot + c = g + [0; tau_m + passive] + sum_c J_c^T f_c  for the generalised velocity
+        nu = [w_b (3); v_b (3); qd (21)] = state words 7:13 | 34:55 (base twist in body coordinates; joints in get_state()'s order, about
+        the +axis).  Returns a dict of tensors on the env's device (numpy arrays in numpy mode), m rows in env_ids order, holding the
+        groups asked for:
+          mass:      mass [m,27,27]: joint-space inertia with the rotor armature on the joint diagonal, symmetric bit for bit;
+          forces:    bias [m,27] (velocity-product force c), gravity [m,27] (generalised force of gravity g), passive [m,27] (joint
+                     springs, dampers and limits in continuous time; 0 on the base);
+          jacobians: corner_jac [m,8,3,27]: world velocity of sole corner 4 * foot + k (foot 0 = right) per unit nu."""
+        if not hasattr(self.backend, "eom"):
+            raise NotImplementedError("this backend has no equation-of-motion readout")
+        if not (mass or forces or jacobians):
+            raise ValueError("equation_of_motion: ask for at least one of mass, forces, jacobians")
+        if env_ids is None:
+            ids, m = None, self.num_envs
+        else:
+            _, host_ids = self._env_ids(env_ids, allow_mask=False)
+            m = int(host_ids.size)
+            ids = torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        new = lambda *shape: torch.empty((m,) + shape, dtype=torch.float32, device=self.device)
+        ma = new(_lib.EOM_DOF, _lib.EOM_DOF) if mass else None
+        fo = new(_lib.EOM_FORCES, _lib.EOM_DOF) if forces else None
+        ja = new(_lib.KIN_CORNER, 3, _lib.EOM_DOF) if jacobians else None
+        if m:
+            self.backend.eom(ids, m, ma, fo, ja)
+        out = {}
+        if mass:
+            out["mass"] = ma
+        if forces:
+            out.update(bias=fo[:, 0], gravity=fo[:, 1], passive=fo[:, 2])
+        if jacobians:
+            out["corner_jac"] = ja
+        return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
+
     @property
     def unwrapped(self):
         return self
@@ -775,6 +816,11 @@ class SteppingStoneEnv:
     def step_forces(self, action):
         """Dry run of step(action) from the current state (SteppingStoneVecEnv.step_forces): the dict without the env axis."""
         out = self.vec.step_forces(np.asarray(action, np.float32).reshape(1, ACT_DIM))
+        return {k: v[0] for k, v in out.items()}
+
+    def equation_of_motion(self, mass=True, forces=True, jacobians=True):
+        """The terms of the equation of motion at the current state (SteppingStoneVecEnv.equation_of_motion): the dict without the env axis."""
+        out = self.vec.equation_of_motion(mass=mass, forces=forces, jacobians=jacobians)
         return {k: v[0] for k, v in out.items()}
 
     def render(self, mode="rgb_array", width=256, height=192, camera=None):
