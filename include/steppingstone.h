@@ -205,7 +205,8 @@ int ss_version(void);
  * ss_camera: mode SS_CAM_TRACK (default) -- target = torso position + target[], eye = target + eye[] (world-frame offsets);
  * SS_CAM_CHASE -- the same with both offsets turned by the torso's yaw (per-env pixel observations); SS_CAM_FIXED -- eye[] and
  * target[] in world coordinates.  Vertical field of view fov_y_deg in (0, 180); far_m > 0 (depth of the background, and no hit at or
- * beyond it counts); flags bit 0: hard shadows.  ss_camera_default fills the TRACK camera that frames a reset robot and its next stone. */
+ * beyond it counts); flags bit 0: hard shadows.  eye[] and target[] must be finite and the view vector (eye[] for TRACK / CHASE,
+ * target[] - eye[] for FIXED) at least 1e-6 m long: a camera without a view direction is refused.  ss_camera_default fills the TRACK camera that frames a reset robot and its next stone. */
 typedef enum { SS_CAM_TRACK = 0, SS_CAM_CHASE = 1, SS_CAM_FIXED = 2 } ss_camera_mode;
 #define SS_CAM_SHADOWS 1
 typedef struct {

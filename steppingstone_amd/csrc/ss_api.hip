@@ -2,6 +2,7 @@
 // structure-of-arrays state and launches the gfx950 kernels on the caller's stream.  There is no CPU path.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -764,6 +765,19 @@ int ss_render(ss_env* env, const int32_t* env_ids, int32_t m, int32_t width, int
     return fail(SS_ERR_INVALID, "ss_render: camera mode must be SS_CAM_TRACK, SS_CAM_CHASE or SS_CAM_FIXED");
   if (!(cam->fov_y_deg > 0.f && cam->fov_y_deg < 180.f) || !(cam->far_m > 0.f && cam->far_m < 3.0e38f))
     return fail(SS_ERR_INVALID, "ss_render: fov_y_deg must lie in (0, 180) and far_m be positive and finite");
+  {
+    // the view vector (docs/RENDER.md 1): the eye offset for TRACK / CHASE, target - eye for FIXED.  camera_setup normalises it.
+    float v2 = 0.f;
+    bool finite = true;
+    for (int i = 0; i < 3; ++i) {
+      const float ei = cam->eye[i], ti = cam->target[i];
+      finite = finite && std::isfinite(ei) && std::isfinite(ti);
+      const float v = cam->mode == SS_CAM_FIXED ? ti - ei : ei;
+      v2 += v * v;
+    }
+    if (!finite || !(v2 >= 1e-12f))
+      return fail(SS_ERR_INVALID, "ss_render: eye and target must be finite and the view vector at least 1e-6 m long");
+  }
   if (((uintptr_t)rgb & 3) || ((uintptr_t)seg & 3) || ((uintptr_t)depth & 3))
     return fail(SS_ERR_INVALID, "ss_render: rgb, depth and seg must be 4-byte aligned");
   SS_HIP(hipSetDevice(env->device));

@@ -253,4 +253,5 @@ def compare(frame, ref, label=""):
     cerr = np.abs(rgb.astype(int) - rrgb.astype(int)).max(axis=-1)
     assert (cerr[smooth] <= 2).all(), "%s: rgb off by up to %d at %s" % (label, cerr[smooth].max(),
                                                                            np.argwhere(smooth & (cerr > 2))[:5].tolist())
-    return dict(seg_mismatch=int(bad.sum()), depth_err=float(derr[ok].max()) if ok.any() else 0.0, rgb_err=int(cerr[smooth].max()))
+    return dict(seg_mismatch=int(bad.sum()), depth_err=float(derr[ok].max()) if ok.any() else 0.0,
+                rgb_err=int(cerr[smooth].max()) if smooth.any() else 0)         # a 4 x 4 frame can be all edges

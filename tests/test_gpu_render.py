@@ -1,6 +1,8 @@
 """The render kernels on the GPU (docs/RENDER.md): body poses against model.fk, frames against the numpy restatement
 (tests/np_render.py) with the tolerances of tests/test_render_host.py, determinism and batch independence, read-only-ness, argument
-checks, hipGraph capture, and the Python surface (render / get_images / make_env(render=True) / python -m steppingstone_amd.enjoy)."""
+checks, hipGraph capture, and the Python surface (render / get_images / make_env(render=True) / python -m steppingstone_amd.enjoy).
+The second half holds render_kernel's own write-out: frame sizes whose last tiles are partial under the cameras of tests/render_cases.py,
+ss_render itself on pre-filled buffers with canary tails, each output alone, repeated and invalid ids."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +10,7 @@ import pytest
 import torch
 
 import np_render as nr
+import render_cases as rc
 
 pytestmark = pytest.mark.gpu
 ENVS = {"walker3d": "Walker3DStepperEnv-v0", "mike": "MikeStepperEnv-v0"}
@@ -107,8 +110,11 @@ def test_invalid_arguments_and_out_of_range_ids():
     torch.cuda.synchronize()
     bad_mode, bad_fov = _lib.default_camera(), _lib.default_camera()
     bad_mode.mode, bad_fov.fov_y_deg = 3, 0.0
+    no_view = _cam(eye=(0.0, 0.0, 0.0))                                             # TRACK: the eye offset is the view vector
+    no_view_fixed = _cam(mode=nr.FIXED, eye=(1.0, 2.0, 3.0), target=(1.0, 2.0, 3.0 + 5e-7))
+    nan_eye = _cam(mode=nr.CHASE, eye=(-0.9, float("nan"), 0.45))
     for kw in (dict(m=0), dict(m=-1), dict(w=30), dict(h=18), dict(w=2052), dict(h=4096), dict(w=0), dict(rgb=None), dict(cam=bad_mode),
-               dict(cam=bad_fov)):
+               dict(cam=bad_fov), dict(cam=no_view), dict(cam=no_view_fixed), dict(cam=nan_eye)):
         assert ok(**kw) == -1, kw                            # SS_ERR_INVALID
         assert lib.ss_last_error()
     assert lib.ss_render(h, p(ids), 2, 32, 32, None, p(rgb), None, None, None) == -1
@@ -192,3 +198,106 @@ def test_enjoy_module(tmp_path, capsys):
     ppo.save_checkpoint(ppo.ActorCritic(), str(ck))
     anim = enjoy.run("MikeStepperEnv-v0", str(ck), envs=1, steps=5, size=(32, 32), camera="chase", log=lambda *a: None)
     assert anim.shape == (5, 32, 32, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# render_kernel's own write-out (LDS staging, dword stores of partial tiles) and the cameras of tests/render_cases.py
+TAIL = 64                                                     # canary bytes (rgb, seg) / words (depth) behind each buffer
+PART_N, PART_IDS = 8, [6, 1]
+
+
+def _np_cam(cam):
+    from steppingstone_amd.envs import make_camera
+    return make_camera(cam["mode"], cam["eye"], cam["target"], cam["fov_y_deg"], cam["far_m"], cam["shadows"])
+
+
+def _raw(e, ids, W, H, cam, fill, which=("rgb", "depth", "seg")):
+    """ss_render itself on buffers pre-filled with the byte `fill`, each with a canary tail: -> (rc, {name: array with its tail})"""
+    from steppingstone_amd.envs import _ptr, _stream
+    m = len(ids)
+    count = {"rgb": m * H * W * 3, "depth": m * H * W, "seg": m * H * W}
+    kind = {"rgb": torch.uint8, "depth": torch.int32, "seg": torch.uint8}
+    bufs = {k: torch.full((count[k] + TAIL,), fill if k != "depth" else (-1 if fill else 0), dtype=kind[k], device="cuda:0") for k in which}
+    dev_ids = torch.as_tensor(ids, dtype=torch.int32).to("cuda:0")
+    ptr = lambda k: _ptr(bufs[k]) if k in bufs else None
+    rc = e.backend.lib.ss_render(e.backend.h, _ptr(dev_ids), m, W, H, C.byref(_np_cam(cam)), ptr("rgb"), ptr("depth"), ptr("seg"),
+                                 _stream(e.device))
+    torch.cuda.synchronize()
+    return rc, {k: v.cpu().numpy() for k, v in bufs.items()}
+
+
+def _frames(e, ids, W, H, cam, which=("rgb", "depth", "seg")):
+    """the call with fill 0x00 and with fill 0xFF: the tails intact and the two results identical -- every byte inside was written and none
+    outside -- -> {rgb [m,H,W,3] u8, depth [m,H,W] f32, seg [m,H,W] u8} of those asked for"""
+    m = len(ids)
+    shape = {"rgb": (m, H, W, 3), "depth": (m, H, W), "seg": (m, H, W)}
+    outs = []
+    for fill in (0x00, 0xFF):
+        rc, bufs = _raw(e, ids, W, H, cam, fill, which)
+        assert rc == 0
+        out = {}
+        for k, v in bufs.items():
+            canary = v.dtype.type(fill if k != "depth" else (-1 if fill else 0))
+            assert (v[-TAIL:] == canary).all(), "%dx%d: the words behind %s were written" % (W, H, k)
+            body = v[:-TAIL].reshape(shape[k])
+            out[k] = body.view(np.float32) if k == "depth" else body
+        outs.append(out)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k].view(np.uint8), outs[1][k].view(np.uint8)), "%dx%d: %s depends on what the buffer held" % (W, H, k)
+    return outs[0]
+
+
+@pytest.fixture(scope="module", params=["walker3d", "mike"])
+def partial_scene(request):
+    """(kind, an 8-env instance at curriculum 5 after 40 random steps, its packed states)"""
+    kind = request.param
+    e = _env(kind, PART_N, seed=7, cur=5, steps=40)
+    st = e.get_state().cpu().numpy()
+    yield kind, e, st
+    e.close()
+
+
+@pytest.mark.parametrize("size", rc.SIZES, ids=lambda s: "%dx%d" % s)
+def test_partial_tiles_and_other_cameras_match_numpy(partial_scene, size):
+    import render_host_lib as rh
+    kind, e, st = partial_scene
+    W, H = size
+    same = {"rgb": [], "depth": [], "seg": []}
+    for name, cam in rc.cameras(st[PART_IDS[0], 0:3]):
+        got = _frames(e, PART_IDS, W, H, cam)
+        host = dict(zip(("rgb", "depth", "seg"), rh.render(["walker3d", "mike"].index(kind), st, PART_IDS, W, H, cam)))
+        for m, i in enumerate(PART_IDS):
+            ref = nr.render(kind, st[i].astype(np.float64), W, H, cam)
+            nr.compare((got["rgb"][m], got["depth"][m], got["seg"][m]), ref, "%s %dx%d %s env %d" % (kind, W, H, name, i))
+        for k in same:
+            same[k].append(float((got[k].view(np.uint8) == host[k].view(np.uint8)).mean()))
+    print("render device-vs-host %s %dx%d: share of equal bytes over %d cameras: %s"
+          % (kind, W, H, len(same["rgb"]), {k: "%.4f (least %.4f)" % (np.mean(v), min(v)) for k, v in same.items()}))
+
+
+def test_each_output_alone_equals_the_full_call(partial_scene):
+    kind, e, st = partial_scene
+    for name, cam in rc.cameras(st[PART_IDS[0], 0:3])[:4]:
+        full = _frames(e, PART_IDS, 52, 36, cam)
+        for k in ("rgb", "depth", "seg"):
+            alone = _frames(e, PART_IDS, 52, 36, cam, which=(k,))
+            assert set(alone) == {k} and np.array_equal(alone[k].view(np.uint8), full[k].view(np.uint8)), "%s alone, %s" % (k, name)
+
+
+def test_repeated_and_invalid_ids_under_a_fixed_camera(partial_scene):
+    kind, e, st = partial_scene
+    ids = [3, -1, 3, PART_N, 0]
+    name, cam = rc.cameras(st[3, 0:3])[0]
+    assert cam["mode"] == nr.FIXED
+    got = _frames(e, ids, 52, 36, cam)
+    for k in got:
+        assert np.array_equal(got[k][0].view(np.uint8), got[k][2].view(np.uint8)), "a repeated id gives another %s frame" % k
+    back = nr.render(kind, None, 52, 36, cam)
+    for m in (1, 3):
+        assert (got["seg"][m] == 0).all() and (got["depth"][m] == np.float32(cam["far_m"])).all()
+        assert np.abs(got["rgb"][m].astype(int) - back[0]).max() <= 1
+    for m, i in enumerate(ids):
+        alone = _frames(e, [i], 52, 36, cam)
+        for k in got:
+            assert np.array_equal(got[k][m].view(np.uint8), alone[k][0].view(np.uint8)), "row %d (id %d) of %s differs from the env drawn alone" % (m, i, k)
+    assert (got["seg"][0] > 0).any()

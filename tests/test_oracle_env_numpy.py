@@ -64,7 +64,7 @@ def test_control_step_outputs_match_independent_numpy(kind):
 def test_create_temp_states_matches_independent_numpy(kind):
     """PHYSICS.md 8: the current observation with the look-ahead stone n+1 re-placed at each of the 121 grid cells (same step
     length, same tilts), rows in grid order i*11+j."""
-    import np_terrain as npt
+    import temp_states_cases as tsc
     m = npc.rounded_model(kind)
     o = ol.OracleEnv(kind, 12, seed=4, prec="f64")
     o.set_curriculum(5)
@@ -88,15 +88,11 @@ def test_create_temp_states_matches_independent_numpy(kind):
         if n >= 19:
             continue
         moved += n > 1
-        terrain = st[e, ol.S_TERRAIN].reshape(20, 6)
         base = np_env.observation(m, st[e], int(st[e, ol.S_FLAGS]), n)
+        refs = tsc.reference(kind, st[e])                        # all 121 grid cells, fp64
         for i in range(11):
             for j in range(11):
-                s2 = st[e].copy()
-                t2 = s2[ol.S_TERRAIN].reshape(20, 6)
-                phi, dr = terrain[n][3] + npt.YAW[i], st[e, ol.S_NNDR]
-                t2[n + 1][:3] = terrain[n][:3] + dr * np.array([np.cos(npt.PITCH[j]) * np.cos(phi), np.cos(npt.PITCH[j]) * np.sin(phi), np.sin(npt.PITCH[j])])
-                ref = np_env.observation(m, s2, int(st[e, ol.S_FLAGS]), n)
+                ref = refs[i * 11 + j]
                 assert np.array_equal(ref[:55], base[:55])
                 worst = max(worst, np.abs(tmp[e, i * 11 + j].astype(np.float64) - ref).max())
     print("%s: create_temp_states of 12 envs (%d beyond their first target): worst |obs| %.1e" % (kind, moved, worst))

@@ -63,3 +63,28 @@ def test_partial_tiles_and_odd_shapes():
     cam = dict(nr.DEFAULT_CAMERA, shadows=True)
     rgb, depth, seg = rh.render(1, st, [1], 52, 36, cam)
     nr.compare((rgb[0], depth[0], seg[0]), nr.render("mike", st[1].astype(np.float64), 52, 36, cam), "52x36")
+
+
+@pytest.mark.parametrize("kind,k", [("walker3d", 0), ("mike", 1)])
+def test_other_cameras_on_partial_tiles(kind, k):
+    """tests/render_cases.py: FIXED (from the side, straight down and up: the `r` fallback), a close CHASE with a wide field of view, a far
+    TRACK with a narrow one, a far plane that cuts the scene -- at sizes whose tiles are partial."""
+    import render_cases as rc
+    import render_host_lib as rh
+    st = _states(kind, 5)
+    e = 3
+    cams = rc.cameras(st[e, 0:3])
+    assert sum(rc.vertical(c) for _, c in cams) == 2 and {c["mode"] for _, c in cams} == {nr.TRACK, nr.CHASE, nr.FIXED}
+    seen = 0
+    for W, H in rc.HOST_SIZES:
+        for name, cam in cams:
+            rgb, depth, seg = rh.render(k, st, [e], W, H, cam)
+            ref = nr.render(kind, st[e].astype(np.float64), W, H, cam)
+            nr.compare((rgb[0], depth[0], seg[0]), ref, "%s %dx%d %s" % (kind, W, H, name))
+            if (W, H) == (52, 36):
+                assert (ref[2] > 0).mean() > 0.02, "%s: the camera sees nothing" % name
+                cut = name == "default, far 2.6 m"
+                full = nr.render(kind, st[e].astype(np.float64), W, H, dict(cam, far_m=20.0))[2] if cut else None
+                assert not cut or ((full > 0) & (ref[2] == 0)).any(), "the far plane cuts nothing"
+                seen += 1
+    assert seen == len(cams)
