@@ -40,7 +40,7 @@ extern "C" {
                             * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
                             * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
                             * readout (ss_kinematics), the force readout (ss_step_forces) and the equation-of-motion readout
-                            * (ss_eom). */
+                            * (ss_eom), and the impulse (ss_push), the one addition that writes: velocities only. */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -293,6 +293,30 @@ int ss_step_forces(ss_env* env, const int32_t* env_ids, int32_t m, const float* 
 #define SS_EOM_DOF 27      /* 6 base + 21 joints */
 #define SS_EOM_FORCES 3    /* rows of `forces` */
 int ss_eom(ss_env* env, const int32_t* env_ids, int32_t m, float* mass, float* forces, float* corner_jac, void* stream);
+
+/* Impulse: push body body[k] of env env_ids[k] (docs/PHYSICS.md "Impulse" has the definitions); added under version 4 (nothing existing
+ * moved).  delta_nu = M(q)^-1 J^T w: M the `mass` of ss_eom (rotor armature included), nu its generalised velocity (state words 7:13 |
+ * 34:55), J the 6 x 27 Jacobian of the pushed point ([x-dot; omega_b] = J nu, world axes), w the wrench impulse.  Contacts, joint limits
+ * and the implicit damping of PHYSICS.md 3.1 do not enter: the push is instantaneous, positions do not move, and the next substep's
+ * detection and contact solve see the new velocities.  Total linear momentum changes by exactly p, angular momentum about the centre of
+ * mass by (x - com) x p + L.  Ordered on `stream`, never synchronises the host, allocates nothing, can be captured into a graph.
+ *   env_ids: DEVICE [m] int32 with the conventions of ss_eom (NULL: envs 0..m-1, needs m == N; m == 0 does nothing; an id outside [0, N)
+ *     is skipped: nothing of it is read or written).
+ *   body: DEVICE [m] int32 in [0, 22), the bodies of ss_body_poses; NULL: the torso for every row.  An index outside the range lives on
+ *     the device and is not checked here: that row is skipped like a bad id.
+ *   point: DEVICE [m,3] f32, the pushed point in the body's link frame; NULL: the body's centre of mass (the link origin of a massless
+ *     intermediate link).
+ *   impulse: DEVICE [m, SS_PUSH_WRENCH] f32, world axes: 0:3 linear impulse p in N s acting at the point | 3:6 pure angular impulse L in
+ *     N m s.  Required when m > 0.
+ *   delta_nu: DEVICE [m, SS_EOM_DOF] f32, 16-byte aligned, or NULL: receives delta_nu.
+ *   apply != 0: state words 7:13 and 34:55 of env env_ids[k] become nu + delta_nu; no other word, no other env and no RNG counter
+ *     changes.  With repeated ids the result for that env is unspecified, as in ss_set_state_envs; the effect is linear, so two pushes on
+ *     one env are two dry runs added.  apply == 0: a dry run, which needs delta_nu.
+ * Bad host arguments return SS_ERR_INVALID and launch nothing.  A row's delta_nu bits depend on the env's state and on that row's body,
+ * point and impulse alone: not on N, m, k, apply or on delta_nu being asked for.  An all-zero impulse row yields delta_nu exactly 0. */
+#define SS_PUSH_WRENCH 6   /* words of an impulse row */
+int ss_push(ss_env* env, const int32_t* env_ids, int32_t m, const int32_t* body, const float* point, const float* impulse,
+            float* delta_nu, int32_t apply, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

@@ -28,6 +28,9 @@ hipError_t launch_step_forces(const Params& P, int kind, const int32_t* env_ids,
 // compiled in ss_eom.hip (the equation-of-motion readout, docs/PHYSICS.md)
 hipError_t launch_eom(const Params& P, int kind, const int32_t* env_ids, int m, float* mass, float* forces, float* corner_jac,
                       hipStream_t st);
+// compiled in ss_push.hip (the impulse, docs/PHYSICS.md)
+hipError_t launch_push(const Params& P, int kind, const int32_t* env_ids, int m, const int32_t* body, const float* point,
+                       const float* impulse, float* delta_nu, int apply, hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -823,6 +826,20 @@ int ss_eom(ss_env* env, const int32_t* env_ids, int32_t m, float* mass, float* f
     return fail(SS_ERR_INVALID, "ss_eom: mass, forces and corner_jac must be 16-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_eom(env->P, env->kind, env_ids, m, mass, forces, corner_jac, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_push(ss_env* env, const int32_t* env_ids, int32_t m, const int32_t* body, const float* point, const float* impulse,
+            float* delta_nu, int32_t apply, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_push: m must be >= 0");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_push: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (!impulse) return fail(SS_ERR_INVALID, "ss_push: impulse is NULL");
+  if (!apply && !delta_nu) return fail(SS_ERR_INVALID, "ss_push: a dry run (apply == 0) needs delta_nu");
+  if ((uintptr_t)delta_nu & 15) return fail(SS_ERR_INVALID, "ss_push: delta_nu must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_push(env->P, env->kind, env_ids, m, body, point, impulse, delta_nu, apply ? 1 : 0, (hipStream_t)stream));
   return SS_OK;
 }
 

@@ -15,7 +15,11 @@ contact flags, right / left), next_step_index [T,K], done [T,K].
 --forces (only together with --trace) adds the force readout of every step (SteppingStoneVecEnv.step_forces, docs/PHYSICS.md 10), taken
 as a dry run from the state the step STARTS in, with the action the policy chose: contact_force [T,K,4,8,8] (per substep and sole
 corner: carrier slot, penetration, force along n / t1 / t2, force as a world vector) and joint_torque [T,K,4,21] (the torque every joint
-applied over each substep)."""
+applied over each substep).
+
+--push STEP:BODY:px,py,pz (repeatable) shoves every env's robot before control step STEP of the walk (SteppingStoneVecEnv.push,
+docs/PHYSICS.md 12): a linear impulse (px, py, pz) in N s, world axes, at the centre of mass of BODY (an index or a name of
+model.BODY_NAMES).  With --trace the pushes are recorded: push_step [P], push_body [P], push_impulse [P,3], push_delta_nu [P,K,27]."""
 import argparse
 import math
 import os
@@ -26,6 +30,7 @@ import torch
 
 from . import ppo
 from .envs import SteppingStoneVecEnv, make_camera
+from .model import BODY_NAMES
 
 
 def load_policy(path, device):
@@ -55,16 +60,32 @@ def tile(frames):
     return out
 
 
+def parse_push(text):
+    """"STEP:BODY:px,py,pz" -> (step, body index, [px, py, pz])"""
+    try:
+        step, body, imp = text.split(":")
+        p = [float(x) for x in imp.split(",")]
+        b = BODY_NAMES.index(body) if body in BODY_NAMES else int(body)
+        if len(p) != 3 or not 0 <= b < len(BODY_NAMES) or int(step) < 0:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--push takes STEP:BODY:px,py,pz with BODY an index in [0, %d) or one of %s, got %r" % (
+            len(BODY_NAMES), ", ".join(BODY_NAMES), text)) from None
+    return int(step), b, p
+
+
 TRACE_KEYS = ("com", "com_vel", "corner_height", "corner_carrier")
 FORCE_KEYS = ("contact_force", "joint_torque")
 
 
 def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240), camera="track", device="cuda:0", out=None,
-        log=print, trace=None, forces=False):
+        log=print, trace=None, forces=False, pushes=()):
     """Roll the policy out deterministically; returns the [T, H, W, 3] uint8 animation (and writes it to `out` if given; the kinematic
     trace of the module docstring to `trace` if given)."""
     if forces and not trace:
         raise ValueError("forces=True needs a trace file to write to")
+    pushes = [parse_push(p) if isinstance(p, str) else p for p in pushes]
+    pushed = dict(push_step=[], push_body=[], push_impulse=[], push_delta_nu=[])
     ac = load_policy(net, device)
     ac.eval()
     env = SteppingStoneVecEnv(env_id, envs, seed=seed, device=device, return_numpy=False)
@@ -78,7 +99,14 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
     try:
         obs = env.reset()
         ep_reward = torch.zeros(envs, dtype=torch.float64, device=env.device)
-        for _ in range(steps):
+        for t in range(steps):
+            for step, body, p in pushes:
+                if step == t:
+                    dnu = env.push(torch.tensor([p] * envs, dtype=torch.float32), body=body)
+                    log("step %d: pushed %s by (%g, %g, %g) N s" % (t, BODY_NAMES[body], *p))
+                    for k, v in zip(pushed, (step, body, p, dnu.cpu().numpy())):
+                        pushed[k].append(v)
+                    obs = env.get_obs()
             frames.append(tile(env.render("rgb_array", width=W, height=H, camera=cam).cpu().numpy()))
             with torch.no_grad():
                 _, action, _ = ac.act(obs, deterministic=True)
@@ -107,7 +135,9 @@ def run(env_id, net, envs=1, steps=300, curriculum=0, seed=1093, size=(320, 240)
     if trace:
         if not trace.endswith(".npz"):
             trace += ".npz"
-        np.savez(trace, **{k: np.stack(v) for k, v in rec.items()})
+        if pushes:
+            rec.update(pushed)
+        np.savez(trace, **{k: np.stack(v) if v else np.zeros(0) for k, v in rec.items()})
         log("wrote %s (%d steps x %d envs)" % (trace, len(rec["done"]), envs))
     if out:
         save(anim, out, log)
@@ -147,11 +177,14 @@ def main(argv=None):
     p.add_argument("--out", default="enjoy.gif", help=".gif (needs PIL) or .npy")
     p.add_argument("--trace", default=None, metavar="FILE.npz", help="also write COM, sole-corner heights / carriers, contact flags per step")
     p.add_argument("--forces", action="store_true", help="with --trace: also write contact forces and applied joint torques per substep")
+    p.add_argument("--push", action="append", default=[], metavar="STEP:BODY:px,py,pz",
+                   help="shove BODY (index or name) of every env by a linear impulse in N s before control step STEP; repeatable")
     a = p.parse_args(argv)
     if a.forces and not a.trace:
         p.error("--forces needs --trace")
     w, h = (int(x) for x in a.size.lower().split("x"))
-    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out, trace=a.trace, forces=a.forces)
+    run(a.env, a.net, a.envs, a.steps, a.curriculum, a.seed, (w, h), a.camera, a.device, a.out, trace=a.trace, forces=a.forces,
+        pushes=a.push)
     return 0
 
 

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_DIM, GRID, INFO_WORDS, MAX_EPISODE_STEPS, NCELL, NUM_STONES, OBS_DIM, STATE_DIM, SteppingStoneError
+from .model import BODY_NAMES
 
 DEG = np.pi / 180.0
 ENV_KINDS = {
@@ -185,6 +186,14 @@ class HipBackend:
         float32 device tensors or None, not all three (docs/PHYSICS.md 11)."""
         opt = lambda t: _ptr(t) if t is not None else None
         _lib.check(self.lib.ss_eom(self.h, opt(env_ids), int(m), opt(mass), opt(forces), opt(corner_jac), _stream(self.device)))
+
+    def push(self, env_ids, m, body, point, impulse, delta_nu, apply):
+        """env_ids: int32 device tensor [m], or None for envs 0..m-1 (m == N); body: int32 device tensor [m] or None (the torso);
+        point [m,3] or None (the centre of mass); impulse [m,6]; delta_nu [m,27] or None (only with apply): float32 device tensors
+        (docs/PHYSICS.md 12)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_push(self.h, opt(env_ids), int(m), opt(body), opt(point), _ptr(impulse), opt(delta_nu), 1 if apply else 0,
+                                    _stream(self.device)))
 
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
@@ -588,6 +597,60 @@ class SteppingStoneVecEnv:
             out["corner_jac"] = ja
         return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
 
+    def push(self, impulse, env_ids=None, body=0, point=None, apply=True):
+        """Push the envs env_ids names (default: all; the forms of get_state()): a wrench impulse on a body, on the GPU (docs/PHYSICS.md
+        12).  impulse: [m,3], a linear impulse p in N s, or [m,6], p | a pure angular impulse L in N m s, world axes, row k for env
+        env_ids[k]; body: an index in [0, 22), a name of model.BODY_NAMES, or m of either (default: the torso); point: [m,3] or [3], where p
+        acts, in the body's link frame (default: the body's centre of mass).  Returns delta_nu [m,27] = M^-1 J^T w, the change of the
+        generalised velocity nu = state words 7:13 | 34:55 (a tensor on the env's device, a numpy array in numpy mode).  apply=True adds
+        it to the envs' velocities -- nothing else of the state changes, contacts and joint limits act from the next substep on;
+        apply=False is a dry run.  The effect is linear: two pushes on one env are two dry runs added."""
+        if not hasattr(self.backend, "push"):
+            raise NotImplementedError("this backend has no push")
+        if env_ids is None:
+            ids, m = None, self.num_envs
+        else:
+            _, host_ids = self._env_ids(env_ids, allow_mask=False)
+            m = int(host_ids.size)
+            ids = torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        w = torch.as_tensor(impulse, dtype=torch.float32).to(self.device)
+        if w.numel() not in (3 * m, _lib.PUSH_WRENCH * m) or (m == 0 and w.numel() != 0):
+            raise ValueError("push: %d envs need an impulse of shape (%d, 3) or (%d, 6), got %s" % (m, m, m, tuple(w.shape)))
+        w = w.reshape(m, -1) if m else w.reshape(0, _lib.PUSH_WRENCH)
+        if w.shape[1] == 3:
+            w = torch.cat([w, torch.zeros_like(w)], 1)
+        w = w.contiguous()
+        if isinstance(body, (str, int, np.integer)):
+            names = [body] * m
+        else:
+            if not hasattr(body, "__len__"):
+                raise ValueError("push: a body is an index in [0, %d) or a name, got %r" % (_lib.NUM_BODIES, body))
+            names = body.tolist() if hasattr(body, "tolist") else list(body)
+            if len(names) != m:
+                raise ValueError("push: %d envs need one body or %d, got %d" % (m, m, len(names)))
+        idx = []
+        for b in names:
+            if isinstance(b, str):
+                if b not in BODY_NAMES:
+                    raise ValueError("push: no body named %r (model.BODY_NAMES)" % (b,))
+                b = BODY_NAMES.index(b)
+            if not (isinstance(b, (int, np.integer)) and 0 <= b < _lib.NUM_BODIES):
+                raise ValueError("push: a body is an index in [0, %d) or a name, got %r" % (_lib.NUM_BODIES, b))
+            idx.append(int(b))
+        bod = None if all(b == 0 for b in idx) else torch.tensor(idx, dtype=torch.int32).to(self.device)
+        pt = None
+        if point is not None:
+            pt = torch.as_tensor(point, dtype=torch.float32).to(self.device)
+            if pt.numel() == 3:
+                pt = pt.reshape(1, 3).expand(m, 3)
+            if pt.numel() != 3 * m:
+                raise ValueError("push: point must have shape (3,) or (%d, 3), got %s" % (m, tuple(pt.shape)))
+            pt = pt.reshape(m, 3).contiguous()
+        out = torch.zeros((m, _lib.EOM_DOF), dtype=torch.float32, device=self.device)
+        if m:
+            self.backend.push(ids, m, bod, pt, w, out, bool(apply))
+        return out.cpu().numpy() if self.return_numpy else out
+
     @property
     def unwrapped(self):
         return self
@@ -822,6 +885,11 @@ class SteppingStoneEnv:
         """The terms of the equation of motion at the current state (SteppingStoneVecEnv.equation_of_motion): the dict without the env axis."""
         out = self.vec.equation_of_motion(mass=mass, forces=forces, jacobians=jacobians)
         return {k: v[0] for k, v in out.items()}
+
+    def push(self, impulse, body=0, point=None, apply=True):
+        """Push the robot (SteppingStoneVecEnv.push): impulse [3] or [6]; returns delta_nu [27]."""
+        w = np.asarray(impulse, np.float32).reshape(1, -1)
+        return self.vec.push(w, body=body, point=None if point is None else np.asarray(point, np.float32).reshape(1, 3), apply=apply)[0]
 
     def render(self, mode="rgb_array", width=256, height=192, camera=None):
         """One (H, W, 3) uint8 frame of the env (SteppingStoneVecEnv.render); mode="human" raises NotImplementedError."""

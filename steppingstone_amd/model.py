@@ -30,6 +30,14 @@ JOINT_NAMES = [
     "right_shoulder_x", "right_shoulder_z", "right_shoulder_y", "right_elbow",
     "left_shoulder_x", "left_shoulder_z", "left_shoulder_y", "left_elbow",
 ]
+# body b of ss_body_poses / ss_push: the torso, then the child link of joint b - 1.  A massless intermediate link carries its joint's name.
+BODY_NAMES = [
+    "torso", "abdomen_z", "lwaist", "pelvis",
+    "right_hip_x", "right_hip_z", "right_thigh", "right_shin", "right_foot",
+    "left_hip_x", "left_hip_z", "left_thigh", "left_shin", "left_foot",
+    "right_shoulder_x", "right_shoulder_z", "right_upper_arm", "right_lower_arm",
+    "left_shoulder_x", "left_shoulder_z", "left_upper_arm", "left_lower_arm",
+]
 
 # parent BODY index of joint j's child link (child link of joint j is body j+1)
 PARENT = [0, 1, 2,
