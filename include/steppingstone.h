@@ -40,7 +40,8 @@ extern "C" {
                             * episode control (ss_reset_masked, ss_get_state_envs, ss_set_state_envs) were ADDED under version 4: no
                             * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
                             * readout (ss_kinematics), the force readout (ss_step_forces) and the equation-of-motion readout
-                            * (ss_eom), and the impulse (ss_push), the one addition that writes: velocities only. */
+                            * (ss_eom), the impulse (ss_push), the one addition that writes: velocities only, and the look-ahead
+                            * (ss_lookahead), which writes nothing of an env. */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -317,6 +318,34 @@ int ss_eom(ss_env* env, const int32_t* env_ids, int32_t m, float* mass, float* f
 #define SS_PUSH_WRENCH 6   /* words of an impulse row */
 int ss_push(ss_env* env, const int32_t* env_ids, int32_t m, const int32_t* body, const float* point, const float* impulse,
             float* delta_nu, int32_t apply, void* stream);
+
+/* Look-ahead: dry-run `horizon` control steps of ss_step for action sequences (docs/PHYSICS.md "Look-ahead" has the definitions); added
+ * under version 4 (nothing existing moved).  Row k is a BRANCH of env env_ids[k]: horizon control steps from that env's current state
+ * under the action rows act[k, 0..horizon-1, :], on a private copy of everything a step reads or writes (dynamic state, active stones and
+ * headings, the terrain row, target counters, episode statistics, the RNG counter).  NOTHING of the env changes: no state word, no terrain
+ * row, no RNG counter, no knob.  A branch sees what the env itself would see: its target advances, and the stones drawn on an advance,
+ * come from the env's own counter, global id, curriculum and probability grid; ss_set_power applies; the auto-reset switch is ignored (a
+ * branch never resets).  Ordered on `stream`, never synchronises the host, allocates nothing, can be captured into a graph.
+ *   env_ids: DEVICE [m] int32 with the conventions of ss_step_forces (NULL: envs 0..m-1, needs m == N; m == 0 does nothing; an id outside
+ *     [0, N) is skipped: nothing of it is read, no output row of it is written).  Repeated ids are the normal use: B branches of one env
+ *     are B rows with its id.
+ *   horizon: 1 .. SS_LOOK_MAX_STEPS.
+ *   act: DEVICE [m, horizon, 21] f32, policy coordinates, clipped as in ss_step (a NaN ends the episode as there).
+ *   obs: DEVICE [m, horizon, 60] f32 or NULL; rew: DEVICE [m, horizon] f32; done: DEVICE [m, horizon] u8: for every step s up to and
+ *     including the first with done, bit for bit what ss_step writes for that env with auto-reset off, stepped s + 1 times under the same
+ *     actions (the time limit counts).  Every later step of the row: done = 1, rew = 0.0f, the observation repeats the terminal row.
+ *   final_state: DEVICE [m, SS_STATE_DIM] f32 or NULL: bit for bit ss_get_state_envs of the env after those real steps -- the state the
+ *     finishing step ended in, or the state after step horizon - 1.
+ *   work: DEVICE [m, SS_LOOK_WORK] f32, required when m > 0: where a branch keeps its private copy; its contents afterwards are
+ *     unspecified.
+ *   obs, rew, final_state and work are 16-byte aligned.
+ * Bad host arguments return SS_ERR_INVALID and launch nothing.  A row's bits depend on the env's state, the knobs and that row's actions
+ * alone: not on N, m, k, repeated ids, on which outputs were asked for, or on the steps behind them (the first H' steps of a call with
+ * horizon > H' are those of a call with horizon H'). */
+#define SS_LOOK_MAX_STEPS 1000          /* = SS_MAX_EPISODE_STEPS */
+#define SS_LOOK_WORK 160                /* f32 words of workspace per row */
+int ss_lookahead(ss_env* env, const int32_t* env_ids, int32_t m, int32_t horizon, const float* act,
+                 float* obs, float* rew, uint8_t* done, float* final_state, float* work, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

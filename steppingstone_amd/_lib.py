@@ -21,13 +21,14 @@ SYMBOLS = [
     "ss_peer_alloc", "ss_peer_free", "ss_peer_ipc_handle", "ss_peer_ipc_open", "ss_peer_ipc_close", "ss_peer_connect",
     "ss_step_packed_peers", "ss_peer_wait", "ss_peer_error", "ss_rollout_random_packed", "ss_debug_set_id_mask",
     "ss_camera_default", "ss_body_poses", "ss_render", "ss_reset_masked", "ss_get_state_envs", "ss_set_state_envs",
-    "ss_kinematics", "ss_step_forces", "ss_eom", "ss_push",
+    "ss_kinematics", "ss_step_forces", "ss_eom", "ss_push", "ss_lookahead",
 ]
 NUM_BODIES = 22           # torso + 21 links: ss_body_poses rows per env
 KIN_SUMMARY, KIN_CORNER = 12, 8   # SS_KIN_SUMMARY, SS_KIN_CORNER: words of a summary row, sole corners per env (ss_kinematics)
 FRC_SUBSTEPS, FRC_CONTACT, FRC_JOINT, FRC_STATE = 4, 8, 4, 56   # SS_FRC_*: substeps, words per corner row, joint rows, next_state words
 EOM_DOF, EOM_FORCES = 27, 3        # SS_EOM_DOF, SS_EOM_FORCES: generalised coordinates (6 base + 21 joints), rows of `forces` (ss_eom)
 PUSH_WRENCH = 6                    # SS_PUSH_WRENCH: words of an impulse row, p | L (ss_push)
+LOOK_MAX_STEPS, LOOK_WORK = 1000, 160   # SS_LOOK_MAX_STEPS, SS_LOOK_WORK: longest horizon, f32 words of workspace per row (ss_lookahead)
 CAM_TRACK, CAM_CHASE, CAM_FIXED = 0, 1, 2     # ss_camera.mode
 CAM_SHADOWS = 1                                # ss_camera.flags bit 0
 
@@ -103,6 +104,7 @@ def load():
     lib.ss_step_forces.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     lib.ss_eom.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.ss_push.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.ss_lookahead.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     if lib.ss_version() != ABI_VERSION:
         # the argument lists and struct sizes changed between versions (2: steps_per_launch in ss_rollout_random; 3: ss_info has 6
         # words, the packed state 186): a stale library would be called with the wrong layout and no error

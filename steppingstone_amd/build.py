@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libsteppingstone.so")
-SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip", "ss_forces.hip", "ss_eom.hip", "ss_push.hip"]
+SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip", "ss_forces.hip", "ss_eom.hip", "ss_push.hip", "ss_lookahead.hip"]
 # ss_rollout3.hip (the three-helper rollout kernel) is compiled without the max-ILP scheduling strategy: see its header.  So is
 # ss_render.hip: the render kernel is 9 % faster without it (4096 envs at 64 x 64, RGB + depth + seg, shadows: 0.889 against 0.977 ms
 # per call; DESIGN.md "Rendering").  So is ss_kinematics.hip: the strategy buys the readout no time and costs it registers -- 64 VGPRs
@@ -27,8 +27,11 @@ SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"
 # per lane and 41 536 B of LDS (occupancy 2 waves per SIMD either way), so the resources give no reason to leave the default
 # ss_push.hip (the impulse) keeps it too: 243 against 242 VGPRs, 148 B of scratch, 54 688 B of LDS and occupancy 2 either way, and 63.5
 # against 63.2 us per call at 4096 envs, 432.7 against 434.9 at 32768
+# ss_lookahead.hip (the look-ahead: the plain step kernel's substeps, H control steps per launch) keeps it: 256 VGPRs + 254 AGPRs and no
+# scratch with it, 256 + 256 and 180 B per lane without, and 1074 against 1112 us per call of 16 steps at 4096 rows, 1138 against 1188
+# at 32768
 NO_MAX_ILP = {"ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"}
-HEADERS = ["ss_math.hpp", "ss_pair.hpp", "ss_dynamics.hpp", "ss_kernels.hpp", "ss_model_tables.hpp", "ss_render.hpp", "ss_visual_tables.hpp", "ss_kinematics.hpp", "ss_forces.hpp", "ss_eom.hpp", "ss_push.hpp",
+HEADERS = ["ss_math.hpp", "ss_pair.hpp", "ss_dynamics.hpp", "ss_kernels.hpp", "ss_model_tables.hpp", "ss_render.hpp", "ss_visual_tables.hpp", "ss_kinematics.hpp", "ss_forces.hpp", "ss_eom.hpp", "ss_push.hpp", "ss_lookahead.hpp",
            os.path.join("..", "..", "include", "steppingstone.h")]
 # -O3 without the SLP vectorizer, signed zeros not honoured.  Measured on gfx950 / ROCm 7.2:
 #   * SLP vectorisation (packed v_pk_fma_f32 / v_pk_mul_f32) miscompiled the 1-env-per-lane kernel of v1-v3 (wrong,

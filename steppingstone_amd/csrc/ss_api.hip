@@ -31,6 +31,9 @@ hipError_t launch_eom(const Params& P, int kind, const int32_t* env_ids, int m, 
 // compiled in ss_push.hip (the impulse, docs/PHYSICS.md)
 hipError_t launch_push(const Params& P, int kind, const int32_t* env_ids, int m, const int32_t* body, const float* point,
                        const float* impulse, float* delta_nu, int apply, hipStream_t st);
+// compiled in ss_lookahead.hip (the look-ahead, docs/PHYSICS.md)
+hipError_t launch_lookahead(const Params& P, int kind, const int32_t* env_ids, int m, int horizon, const float* act, float* obs, float* rew,
+                            uint8_t* done, float* final_state, float* work, hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -840,6 +843,21 @@ int ss_push(ss_env* env, const int32_t* env_ids, int32_t m, const int32_t* body,
   if ((uintptr_t)delta_nu & 15) return fail(SS_ERR_INVALID, "ss_push: delta_nu must be 16-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_push(env->P, env->kind, env_ids, m, body, point, impulse, delta_nu, apply ? 1 : 0, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_lookahead(ss_env* env, const int32_t* env_ids, int32_t m, int32_t horizon, const float* act, float* obs, float* rew, uint8_t* done,
+                 float* final_state, float* work, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_lookahead: m must be >= 0");
+  if (horizon < 1 || horizon > SS_LOOK_MAX_STEPS) return fail(SS_ERR_INVALID, "ss_lookahead: horizon must be in [1, SS_LOOK_MAX_STEPS]");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_lookahead: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (((uintptr_t)obs | (uintptr_t)rew | (uintptr_t)final_state | (uintptr_t)work) & 15)
+    return fail(SS_ERR_INVALID, "ss_lookahead: obs, rew, final_state and work must be 16-byte aligned");
+  if (!act || !rew || !done || !work) return fail(SS_ERR_INVALID, "ss_lookahead: act, rew, done and work are required when m > 0");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_lookahead(env->P, env->kind, env_ids, m, horizon, act, obs, rew, done, final_state, work, (hipStream_t)stream));
   return SS_OK;
 }
 

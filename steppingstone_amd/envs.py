@@ -195,6 +195,13 @@ class HipBackend:
         _lib.check(self.lib.ss_push(self.h, opt(env_ids), int(m), opt(body), opt(point), _ptr(impulse), opt(delta_nu), 1 if apply else 0,
                                     _stream(self.device)))
 
+    def lookahead(self, env_ids, m, horizon, act, obs, rew, done, final_state, work):
+        """env_ids: int32 device tensor [m] (repeats welcome), or None for envs 0..m-1 (m == N); act [m,H,21]; obs [m,H,60] or None, rew
+        [m,H], final_state [m,186] or None, work [m, LOOK_WORK]: float32 device tensors; done [m,H] uint8 (docs/PHYSICS.md 13)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_lookahead(self.h, opt(env_ids), int(m), int(horizon), _ptr(act), opt(obs), _ptr(rew), _ptr(done),
+                                         opt(final_state), _ptr(work), _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
@@ -651,6 +658,59 @@ class SteppingStoneVecEnv:
             self.backend.push(ids, m, bod, pt, w, out, bool(apply))
         return out.cpu().numpy() if self.return_numpy else out
 
+    def lookahead(self, actions, env_ids=None, obs=True, final_state=False):
+        """Dry run of H control steps per action sequence, on the GPU, from the envs' current state, which stays as it is: no state
+        word, no terrain row, no RNG counter changes (docs/PHYSICS.md 13).  actions: [m,H,21], row k a BRANCH of env env_ids[k] (ids in
+        [0, N), repeats welcome: B branches of an env are B rows with its id; [N,H,21] without env_ids), or [N,B,H,21] without env_ids:
+        B branches of every env, and every result below comes back as [N,B,...].  Policy coordinates, clipped as in step().  A branch
+        sees the stones, target advances and time limit the env would see under those actions and never resets: after its first done
+        step its rewards are 0, its done flags True and its observation repeats.  Returns a dict of tensors on the env's device (numpy
+        arrays in numpy mode): rew [m,H], done [m,H] bool, ret [m] (the sum of the branch's rewards), obs [m,H,60] if asked for,
+        final_state [m,186] if asked for (the get_state() row the branch ends in: set_state_envs commits it)."""
+        if not hasattr(self.backend, "lookahead"):
+            raise NotImplementedError("this backend has no look-ahead")
+        act = torch.as_tensor(actions, dtype=torch.float32).to(self.device).contiguous()
+        lead = None
+        if act.dim() == 4:
+            if env_ids is not None or act.shape[0] != self.num_envs or act.shape[3] != ACT_DIM:
+                raise ValueError("lookahead: four-dimensional actions are (%d, B, H, %d) without env_ids, got %s"
+                                 % (self.num_envs, ACT_DIM, tuple(act.shape)))
+            lead = (self.num_envs, int(act.shape[1]))
+            host_ids = np.repeat(np.arange(self.num_envs, dtype=np.int64), lead[1])
+            act = act.reshape(lead[0] * lead[1], act.shape[2], ACT_DIM)
+        elif env_ids is None:
+            host_ids = None
+        else:
+            ids = env_ids.detach().cpu().numpy() if torch.is_tensor(env_ids) else np.asarray(env_ids)
+            if ids.size and (ids.ndim > 1 or not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError("env ids must be a one-dimensional sequence of integers, got dtype %s shape %s" % (ids.dtype, ids.shape))
+            host_ids = ids.reshape(-1).astype(np.int64)
+            if host_ids.size and (host_ids.min() < 0 or host_ids.max() >= self.num_envs):
+                raise ValueError("env ids must lie in [0, %d), got %d..%d" % (self.num_envs, host_ids.min(), host_ids.max()))
+        m = self.num_envs if host_ids is None else int(host_ids.size)
+        if act.dim() != 3 or act.shape[0] != m or act.shape[2] != ACT_DIM:
+            raise ValueError("lookahead: %d branches need actions of shape (%d, H, %d), got %s" % (m, m, ACT_DIM, tuple(act.shape)))
+        horizon = int(act.shape[1])
+        if not 1 <= horizon <= _lib.LOOK_MAX_STEPS:
+            raise ValueError("lookahead: the horizon must lie in [1, %d], got %d" % (_lib.LOOK_MAX_STEPS, horizon))
+        ids = None if host_ids is None else torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        new = lambda *shape: torch.zeros((m,) + shape, dtype=torch.float32, device=self.device)
+        rew = new(horizon)
+        done = torch.ones((m, horizon), dtype=torch.uint8, device=self.device)
+        ob = new(horizon, OBS_DIM) if obs else None
+        fs = new(STATE_DIM) if final_state else None
+        if m:
+            work = torch.empty((m, _lib.LOOK_WORK), dtype=torch.float32, device=self.device)
+            self.backend.lookahead(ids, m, horizon, act, ob, rew, done, fs, work)
+        out = {"rew": rew, "done": done.bool(), "ret": rew.sum(1)}
+        if obs:
+            out["obs"] = ob
+        if final_state:
+            out["final_state"] = fs
+        if lead is not None:
+            out = {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
+        return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
+
     @property
     def unwrapped(self):
         return self
@@ -880,6 +940,13 @@ class SteppingStoneEnv:
         """Dry run of step(action) from the current state (SteppingStoneVecEnv.step_forces): the dict without the env axis."""
         out = self.vec.step_forces(np.asarray(action, np.float32).reshape(1, ACT_DIM))
         return {k: v[0] for k, v in out.items()}
+
+    def lookahead(self, actions, obs=True, final_state=False):
+        """Dry run of B action sequences from the current state (SteppingStoneVecEnv.lookahead): actions [B,H,21] (or [H,21]: one
+        branch) -> the dict with B rows."""
+        a = np.asarray(actions, np.float32)
+        a = a.reshape((-1,) + a.shape[-2:])
+        return self.vec.lookahead(a, env_ids=np.zeros(a.shape[0], np.int64), obs=obs, final_state=final_state)
 
     def equation_of_motion(self, mass=True, forces=True, jacobians=True):
         """The terms of the equation of motion at the current state (SteppingStoneVecEnv.equation_of_motion): the dict without the env axis."""
