@@ -88,6 +88,29 @@ constexpr int kHandSlots = (kHandFloats + 3) / 4;  // float4-slots per lane
 static_assert(kLdsSlots + kHandSlots <= 80, "two helper-variant workgroups must fit the 160 KiB of a CU (16384 envs: 512 workgroups)");
 static_assert(kHandRows + 40 <= kHandJc + 8 * kRecWords, "rows fit the leg records' place");
 constexpr int kHandBase = kLdsSlots * kWave * 4;   // in floats
+// The far base (device builds).  A DS instruction's offset field has 16 bits, and the hand-off words from index 96 up lie beyond
+// byte 65536 of the workgroup's LDS: addressed from the lane's own base (4 lane) each of them needs a full address in a register of its
+// own (a v_or_b32 with a literal per access) and is read by a single ds_read_b32, because two addresses in two registers do not
+// merge.  Lds::hs() reaches them from ONE further register per lane instead, the byte address of word kFarWord0, made opaque so
+// that the compiler cannot fold it back into literals; the rest of the address is then a constant below 65536 that fits the offset
+// field, and a multiple of 256, so that neighbouring words pair up as ds_read2st64_b32 / ds_write2st64_b32.  kFarWord0 is the first
+// word of Lc, three words before byte 65536: Lc (and cos / sin, which alias it) would otherwise straddle the two bases, and its 18
+// pairs {word 93 + 2 k, word 94 + 2 k} are what one ds_read2st64_b32 each delivers into an aligned register pair.  Same words at the
+// same places: only how their address is formed changes.
+constexpr int kFarWord0 = kHandLc;
+constexpr int kFarBytes = (kHandBase + kFarWord0 * kWave) * 4;                      // of lane 0
+static_assert(kFarBytes <= 65536, "every hand-off word beyond the offset field of the lane's own base goes through the far base");
+constexpr bool hand_far(int idx) { return idx >= kFarWord0; }
+constexpr int hand_far_offset(int idx) { return (idx - kFarWord0) * kWave * 4; }    // bytes behind the far base
+constexpr int lds_bytes(int helpers) { return (kLdsSlots + hand_slots(helpers)) * kWave * 16; }
+constexpr int hand_last_word(int helpers) { return hand_slots(helpers) * 4 - 1; }   // of the variant's allocation
+static_assert(kHandFloats3 - 1 <= hand_last_word(3) && kHandFloats + 2 - 1 <= hand_last_word(1), "the words in use (one helper: + kHandOut2's two) are allocated");
+static_assert(kFarBytes + (kWave - 1) * 4 + hand_far_offset(hand_last_word(1)) + 4 <= lds_bytes(1), "one helper: far base + largest word is inside the allocation");
+static_assert(kFarBytes + (kWave - 1) * 4 + hand_far_offset(hand_last_word(3)) + 4 <= lds_bytes(3), "three helpers: far base + largest word is inside the allocation");
+static_assert(hand_far_offset(kFarWord0) == 0 && hand_far_offset(hand_last_word(3)) < 65536 && hand_far_offset(hand_last_word(1)) < 65536,
+              "every far offset fits the 16-bit offset field");
+static_assert(hand_far_offset(1) - hand_far_offset(0) == 256 && hand_far_offset(hand_last_word(3)) / 256 <= 255,
+              "far offsets are multiples of 256 B within ds_*2st64_b32's reach");
 constexpr int NH = 12;                 // joints per half
 enum { S_ACT = 0, S_Q = 12, S_QD = 24, S_WLAM = 36, S_POS = 48, S_QUAT = 51, S_VW = 55, S_VV = 58, S_STP = 61, S_STN = 70,
        S_WKEY = 79, S_END = 80 };
@@ -189,7 +212,16 @@ struct Lds {       // lane-private view of the workgroup's LDS
   int lane;
   SSD float2& q2(int item) const { return reinterpret_cast<float2*>(base)[item * kWave + lane]; }   // region A, 8-B items
   SSD float& s(int idx) const { return base[kScalarBase + idx * kWave + lane]; }   // region B scalar
-  SSD float& hs(int idx) const { return base[kHandBase + idx * kWave + lane]; }    // hand-off scalar (helper variant)
+  SSD float& hs(int idx) const {                                                   // hand-off scalar (helper variant)
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (hand_far(idx)) {               // the far base (above).  An integer offset is made opaque, not the pointer: the access stays a
+      int off = kFarBytes + lane * 4;  // DS instruction.  The statement is not volatile, so the copies of one wavefront's code merge
+      asm("" : "+v"(off));             // into one (three-helper K-step kernel: one v_or_b32 per wavefront role, outside the substep loop)
+      return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off + hand_far_offset(idx));
+    }
+#endif
+    return base[kHandBase + idx * kWave + lane];
+  }
 };
 
 struct Stones {    // the three active stones n-1, n, n+1: centre, unit normal, tilts (x, y)
