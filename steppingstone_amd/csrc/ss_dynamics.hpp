@@ -71,6 +71,14 @@ constexpr bool spine_packed(int helpers) { return helpers >= 3; }
 // register to spare (docs/HISTORY.md "Joint torques of the {leg, arm} pairs on packed instructions").  Values are the same either way,
 // bit for bit (tests/test_pair_response.py).
 constexpr bool torques_paired(int helpers, bool kstep) { return helpers >= 3 && kstep; }
+// The contact response (imp_up / chol6_solve_neg / imp_down at the end of solve()) of the three-helper K-step kernel takes the eight
+// spine + leg joint records and the base factor back from the hand-off words 0..92, where the main wavefront itself put them before
+// barriers #1 and #2 (put_rec / put_chol) and where nothing overwrites them before the next substep's #0b (the rows have kHandRows3, the
+// bias words come after the next #0b), instead of carrying them through the rows and the PGS: held in registers they were parked in
+// AGPRs, two issue slots per word, where a ds_read2st64_b32 delivers two words in one.  The loads stand under the last sweep, which
+// covers their latency.  The bits read are the bits written.  Every other kernel keeps its registers: the three-helper one-step kernel
+// measured no gain (docs/HISTORY.md "Contact response: joint records back from the hand-off region").
+constexpr bool response_from_lds(int helpers, bool kstep) { return helpers >= 3 && kstep; }
 constexpr int kHandBias = kHandJc;
 static_assert(24 <= 3 * kRecWords, "biases fit the spine records' place");
 constexpr int kHandRows = kHandJc + 3 * kRecWords;
@@ -1436,11 +1444,12 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
       ssf2 Vp[3] = {{V[0], V[1]}, {V[2], V[3]}, {V[4], V[5]}};
       ssf2 Wp[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
       ssf2 dWp[3];
-      auto sweep = [&]() {           // Gauss-Seidel over the own foot's 12 rows
+      auto sweep_with = [&](auto before_row) {   // Gauss-Seidel over the own foot's 12 rows
 #pragma unroll
         for (int i = 0; i < 3; ++i) dWp[i] = ssf2{0.f, 0.f};
         static_for<0, 12>([&](auto Rc) {
           constexpr int row = decltype(Rc)::value, k = row / 3, d = row % 3;
+          before_row(Rc);
           ssf2 acc = rWp[row][0] * Vp[0];
           acc = rWp[row][1] * Vp[1] + acc;
           acc = rWp[row][2] * Vp[2] + acc;
@@ -1461,6 +1470,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
 #pragma unroll
         for (int i = 0; i < 3; ++i) Wp[i] += dWp[i];
       };
+      auto sweep = [&]() { sweep_with([](auto) {}); };
       constexpr int kCoupled = kPgsIters - 1;   // after the last sweep nothing reads the foot twist any more: its coupling is dead
       ssf2 Cc[6][3];                   // read once (the compiler parks what does not fit in AGPRs: 0.0514 -> 0.0511 ms/step)
 #pragma unroll
@@ -1509,6 +1519,31 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
           }
         }
       }
+#if defined(__HIP_DEVICE_COMPILE__)
+      if constexpr (response_from_lds(HELPERS, KSTEP)) {
+        // The last sweep, and under it the records come back (response_from_lds() above): three groups, each in front of the row from
+        // which the sweep has let go of as many registers as the group takes (Cc is dead behind the loop, every finished row frees its
+        // y = Lambda w), each pinned where it stands -- all in front of the sweep and left to the scheduler, two AGPR moves and six
+        // s_nop get into every pass of the sweep loop (222 instead of 214 per pass).  The leg records the response reads first come
+        // first.  The counts and times of every placement tried: docs/HISTORY.md.
+        sweep_with([&](auto Rc) {
+          constexpr int row = decltype(Rc)::value;
+          if constexpr (row == 0 || row == 5 || row == 9) {
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (row == 0) {
+#pragma unroll
+              for (int k = 7; k >= 5; --k) get_rec(L, k, jc.r[k]);
+            } else if constexpr (row == 5) {
+#pragma unroll
+              for (int k = 4; k >= 0; --k) get_rec(L, k, jc.r[k]);
+            } else {
+              get_chol(L, jc.L0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        });
+      } else
+#endif
       sweep();
       SV W = {{Wp[0].x, Wp[0].y, Wp[1].x}, {Wp[1].y, Wp[2].x, Wp[2].y}};
       // what the next substep of this control step starts from
