@@ -5,8 +5,8 @@
 //
 // The per-lane code re-composes the step kernels' own device functions (substep<Model, 0>, fk_detect, joint_limit, joint_tau) on the
 // plain step kernel's shape: two lanes per env (lane 2r: right half of row r, lane 2r + 1: left half in its y-mirrored world), one
-// wavefront per workgroup, one Lds block.  The load-in lines of step_env that are not a function are restated in load_row below;
-// tests/test_gpu_step_forces.py holds next_state to ss_step's own result bit for bit, which pins them.
+// wavefront per workgroup, one Lds block.  The load-in and the action clip are step_env's own (load_in, put_actions);
+// tests/test_gpu_step_forces.py holds next_state to ss_step's own result bit for bit.
 //
 // Every function is SSD (host and device): tests/host/forces_host.cpp runs the same code on the CPU, the 64 lanes as threads.  The
 // kernel and its launcher are in ss_forces.hip.
@@ -25,11 +25,9 @@ struct Out {
 };
 
 // What a lane remembers across a substep call besides the state in LDS.  The note (two words: the detection of the substep's start and
-// the limit switches of the lane's joints) lives in item 39 of LDS region A, the one item of the block that neither the contact operators
-// (0..35) nor the headings (36..38) use.  The twelve words of Carry are the only values held in registers across the call: as many as the
-// Warm record, which the plain variant of substep leaves unused (its impulses live in S_WLAM / S_WKEY).
-constexpr int kLdsNote = kLdsHead + 3;
-static_assert(kLdsNote < kSlotsA * 2, "the note is inside region A");
+// the limit switches of the lane's joints) lives in kLdsNote (ss_kernels.hpp).  The twelve words of Carry are the only values held in
+// registers across the call: as many as the Warm record, which the plain variant of substep leaves unused (its impulses live in
+// S_WLAM / S_WKEY).
 struct Carry {
   float t[NH];      // tau_j + c_j qd_j / h, this lane's world (c_j: implicit_gain)
 };
@@ -44,51 +42,6 @@ SSD float implicit_gain(float kl, float dl) {
   constexpr float h = kH;
   constexpr float kd = Model::damping[J], ks = Model::stiffness[J];
   return h * (kd + dl) + (h * h) * (ks + kl);
-}
-
-// env state, stones, headings of env e and the clipped, lane-signed action row into the lane's LDS columns: what step_env has in LDS
-// before its first substep (ss_kernels.hpp, "1. this lane's half of the state" and the action clip of "clipped actions")
-SSD void load_row(const Params& P, int e, const float* act_row, int side, float m, const Lds& L) {
-  const size_t np = (size_t)P.npad;
-  const float* F = P.fstate + e;
-  {
-    Cache c0;
-    load_cache(P, e, c0);
-    float h0[3][2];
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) { h0[sl][0] = F[(F_HEAD + sl * 2) * np]; h0[sl][1] = F[(F_HEAD + sl * 2 + 1) * np]; }
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) {
-      L.s(S_STP + sl * 3 + 0) = c0.p[sl][0]; L.s(S_STP + sl * 3 + 1) = m * c0.p[sl][1]; L.s(S_STP + sl * 3 + 2) = c0.p[sl][2];
-      L.s(S_STN + sl * 3 + 0) = c0.nrm[sl][0]; L.s(S_STN + sl * 3 + 1) = m * c0.nrm[sl][1]; L.s(S_STN + sl * 3 + 2) = c0.nrm[sl][2];
-      L.q2(kLdsHead + sl) = make_float2(h0[sl][0], m * h0[sl][1]);
-    }
-  }
-  float gin[13], qin[NH], qdin[NH], ain[NH];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) gin[i] = F[(F_POS + i) * np];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) gin[3 + i] = F[(F_QUAT + i) * np];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) gin[7 + i] = F[(F_VEL + i) * np];
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = left_twin(jr);
-    const int gj = side ? jl : jr;
-    qin[k] = F[(F_Q + gj) * np];
-    qdin[k] = F[(F_QD + gj) * np];
-    ain[k] = act_row[gj];
-  });
-  put_base(L, m, gin, gin + 3, gin + 7, gin + 10);
-  put_joints(L, m, qin, qdin);
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    const float sg = action_lane_sign(jr, m);
-    const float x = ain[k];
-    float a = fminf(fmaxf(x, -1.f), 1.f);
-    a = (x != x) ? x : a;      // a NaN action stays a NaN, as in step_env (PHYSICS.md 4.8)
-    L.s(S_ACT + k) = sg * a;
-  });
 }
 
 // Before substep s: joint rows 0..2 (q, qd, tau of the substep's start), the detection of the substep's start (contacts words 0 and 1),
@@ -199,7 +152,9 @@ SSD void forces_row(const Params& P, const int32_t* env_ids, int m, const float*
   const int e = valid ? e_raw : P.n - 1;
   const float m_ = side ? -1.f : 1.f;                        // y-mirror factor of this lane's world
   const Lds L{lds, lane};
-  load_row(P, e, act + (size_t)row * NJ, side, m_, L);
+  float ain[NH];
+  load_in<true>(P, e, act + (size_t)row * NJ, side, m_, L, ain);      // what step_env has in LDS before its first substep
+  put_actions(L, m_, ain);
 
   const float power = P.knobs->power;
   FootReport fr;

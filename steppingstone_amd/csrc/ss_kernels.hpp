@@ -116,17 +116,39 @@ SSD void place_stone(float px, float py, float pz, float dr, float cp, float sp,
   out_p[1] = py + planar * sph;
   out_p[2] = pz + dr * sp;
 }
-// draw stone k from stone k-1 (terrain table), write it to the table; returns dr and the new stone's data
-SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int k, float out_p[3], float out_n[3],
-                     float out_t[2], float out_h[2], bool store = true) {
+// A stone draw (PHYSICS.md 6) is sample_stone, the read of the predecessor's row of a terrain table, stone_after and the write of the
+// new row.  The two functions are what every table shares; the read and the write stay with the table's owner: draw_stone below for the
+// env's strided table with its provisional stones, look_row (ss_lookahead.hpp) for a branch's contiguous one.
+// One Philox block of env e -> the new stone's distance dr (returned), tilts, and the yaw step and elevation of its sampled cell
+SSD float sample_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, float& xt, float& yt, float& yaw, float& pitch) {
   uint32_t r[4];
   env_block(P, e, ctr, r);
   int cell = sample_cell(P, K, e, u01(r[0]));
   float ratio = (float)K.curriculum / 5.0f;
   float dr = 0.65f + u01(r[1]) * (0.6f * ratio);
   float tilt = 15.0f * kDeg * ratio;
-  float xt = (2.f * u01(r[2]) - 1.f) * tilt, yt = (2.f * u01(r[3]) - 1.f) * tilt;
-  float yaw = yaw_sample(cell / SS_GRID), pitch = pitch_sample(cell % SS_GRID);
+  xt = (2.f * u01(r[2]) - 1.f) * tilt;
+  yt = (2.f * u01(r[3]) - 1.f) * tilt;
+  yaw = yaw_sample(cell / SS_GRID);
+  pitch = pitch_sample(cell % SS_GRID);
+  return dr;
+}
+// ... and the stone itself from its predecessor's centre and heading angle phi: centre, normal, tilts, cos / sin of its heading
+SSD void stone_after(float px, float py, float pz, float phi, float dr, float pitch, float xt, float yt, float out_p[3], float out_n[3],
+                     float out_t[2], float out_h[2]) {
+  float sp, cp, sph, cph;
+  sincosf(pitch, &sp, &cp);
+  sincosf(phi, &sph, &cph);
+  place_stone(px, py, pz, dr, cp, sp, cph, sph, out_p);
+  out_t[0] = xt; out_t[1] = yt;
+  out_h[0] = cph; out_h[1] = sph;
+  stone_normal(phi, xt, yt, out_n);
+}
+// draw stone k from stone k-1 (terrain table), write it to the table; returns dr and the new stone's data
+SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int k, float out_p[3], float out_n[3],
+                     float out_t[2], float out_h[2], bool store = true) {
+  float xt, yt, yaw, pitch;
+  float dr = sample_stone(P, K, e, ctr, xt, yt, yaw, pitch);
   const size_t np = (size_t)P.npad;
   float* T = P.terrain + e;
   // stones from prov_from on are provisional (not stored): the first draw of an episode (k = 3) starts from the provisional
@@ -136,13 +158,7 @@ SSD float draw_stone(const Params& P, const Knobs& K, int e, uint32_t& ctr, int 
   float px = prev_stored ? T[((k - 1) * 6 + 0) * np] : 0.75f * (float)(k - 1);
   float py = prev_stored ? T[((k - 1) * 6 + 1) * np] : 0.f, pz = prev_stored ? T[((k - 1) * 6 + 2) * np] : 0.f;
   float phi = (prev_stored ? T[((k - 1) * 6 + 3) * np] : 0.f) + yaw;
-  float sp, cp, sph, cph;
-  sincosf(pitch, &sp, &cp);
-  sincosf(phi, &sph, &cph);
-  place_stone(px, py, pz, dr, cp, sp, cph, sph, out_p);
-  out_t[0] = xt; out_t[1] = yt;
-  out_h[0] = cph; out_h[1] = sph;
-  stone_normal(phi, xt, yt, out_n);
+  stone_after(px, py, pz, phi, dr, pitch, xt, yt, out_p, out_n, out_t, out_h);
   if (store) {
 #pragma unroll 1
     for (int j = prov; j < k; ++j) {            // (rare: once per episode that gets past its second stone)
@@ -399,6 +415,75 @@ SSD void get_joints(const Lds& L, float m, float (&q)[NH], float (&qd)[NH]) {
     qd[k] = sg * L.s(S_QD + k);
   });
 }
+// ... the active stones (true world) and, where they travel with them (h not null), the cos / sin of their headings
+SSD void put_stones(const Lds& L, float m, const Cache& c, const float (*h)[2] = nullptr) {
+#pragma unroll
+  for (int sl = 0; sl < 3; ++sl) {
+    L.s(S_STP + sl * 3 + 0) = c.p[sl][0]; L.s(S_STP + sl * 3 + 1) = m * c.p[sl][1]; L.s(S_STP + sl * 3 + 2) = c.p[sl][2];
+    L.s(S_STN + sl * 3 + 0) = c.nrm[sl][0]; L.s(S_STN + sl * 3 + 1) = m * c.nrm[sl][1]; L.s(S_STN + sl * 3 + 2) = c.nrm[sl][2];
+    if (h) L.q2(kLdsHead + sl) = make_float2(h[sl][0], m * h[sl][1]);       // the heading in this lane's (y-mirrored) world
+  }
+}
+// this lane's half of an action row [21] ...
+SSD void load_actions(const float* act_row, int side, float (&ain)[NH]) {
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    constexpr int jl = left_twin(jr);
+    ain[k] = act_row[side ? jl : jr];
+  });
+}
+// ... and its way into LDS: clipped to [-1, 1], signed for the lane's world
+SSD void put_actions(const Lds& L, float m, const float (&ain)[NH]) {
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    const float sg = action_lane_sign(jr, m);
+    const float x = ain[k];
+    float a = fminf(fmaxf(x, -1.f), 1.f);
+    a = (x != x) ? x : a;      // a NaN action is not clipped away (fmaxf would): it ends the episode, PHYSICS.md 4.8
+    L.s(S_ACT + k) = sg * a;
+  });
+}
+
+// What a control step has in a lane's LDS columns before its first substep, except the actions: the stones and headings of env e and the
+// lane's half of its dynamic state, mirrored for the left lane.  ACT: this lane's half of act_row is loaded along (ain; put_actions
+// stores it).  Only what the substeps need is loaded here: see step_env.
+template <bool ACT>
+SSD void load_in(const Params& P, int e, const float* act_row, int side, float m, const Lds& L, float (&ain)[NH]) {
+  const size_t np = (size_t)P.npad;
+  const float* F = P.fstate + e;
+  {   // measured: merging these loads with the state loads below is slower (0.0867 vs 0.0857 ms/step)
+    Cache c0;
+    load_cache(P, e, c0);
+    float h0[3][2];
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) { h0[sl][0] = F[(F_HEAD + sl * 2) * np]; h0[sl][1] = F[(F_HEAD + sl * 2 + 1) * np]; }
+    put_stones(L, m, c0, h0);
+  }
+  // this lane's half of the state.  All global loads are issued before the first LDS store: written load-store-load-store the
+  // compiler waited for every load in turn (~25 exposed L2 round trips per step).
+  float gin[13], qin[NH], qdin[NH];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) gin[i] = F[(F_POS + i) * np];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) gin[3 + i] = F[(F_QUAT + i) * np];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) gin[7 + i] = F[(F_VEL + i) * np];
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    constexpr int jl = left_twin(jr);
+    const int gj = side ? jl : jr;
+    qin[k] = F[(F_Q + gj) * np];
+    qdin[k] = F[(F_QD + gj) * np];
+  });
+  if constexpr (ACT) load_actions(act_row, side, ain);
+  put_base(L, m, gin, gin + 3, gin + 7, gin + 10);
+  put_joints(L, m, qin, qdin);
+}
+
+// Item 39 of LDS region A, the one item of the block that neither the contact operators (0..35) nor the headings (36..38) use: two words
+// that a dry-run kernel keeps across its substep calls (ss_forces.hpp, ss_lookahead.hpp; the step kernels leave it alone)
+constexpr int kLdsNote = kLdsHead + 3;
+static_assert(kLdsNote < kSlotsA * 2, "the note is inside region A");
 
 // ---- output stage of a control step: observation / reward / done / info rows and the bulk of the state write-back ----
 struct StepOut {        // what it needs, true world, after the optional reset
@@ -422,6 +507,49 @@ struct StepOut {        // what it needs, true world, after the optional reset
 // lds[g]` evaluates the load first and the loops schedule differently).
 template <class T>
 SSD void copy_out(T* dst, T v) { *dst = v; }
+// The observation row of one env on the lane-pair layout, into its staged row `stage`: every lane the joint entries of its own limbs,
+// the right lane the spine's (stage_obs_joint, for the joints with jr >= 3 || side == 0) and the base / contact / target entries
+// (stage_obs_base).  All values true world.  Two functions: the step kernels store the joint's state between the entries.
+// Joint K of this lane's half: the observation carries POLICY coordinates (PHYSICS.md 2): ps = kPolicySign of THIS joint (left x / z
+// joints: about the mirrored axis; knees: negative in flexion), applied to the true-world angle and to the middle of its true range (a
+// left x / z joint's true range is (-hi, -lo) of its right twin's).  The state arrays keep angles about the +axis.
+template <class Model, int K>
+SSD void stage_obs_joint(float* stage, int side, float q, float qd) {
+  constexpr int jr = kHalf[K];
+  constexpr int jl = left_twin(jr);
+  const int gj = side ? jl : jr;
+  constexpr float midr = 0.5f * (Model::lo[jr] + Model::hi[jr]);
+  constexpr float span = Model::hi[jr] - Model::lo[jr];
+  const float ps = policy_true_sign(jr, side);
+  const float mid = (side && mirror_flips(jr)) ? -midr : midr;
+  stage[6 + gj] = obs_angle(ps, q, mid, span);
+  stage[27 + gj] = obs_rate(ps, qd);
+}
+// obs 0-5 and 48-59: the same entries as in write_obs (see there for the tests that pin the two copies together).  roll .. sy:
+// quat_roll_pitch_cs of the orientation; p1, t1, p2, t2: centre and tilts of the stones n and n+1
+SSD void stage_obs_base(float* stage, const float pos[3], const float quat[4], const SV& v0, float z_init, float roll, float pitch,
+                        float cy, float sy, int flags, const float* p1, const float* t1, const float* p2, const float* t2) {
+  float R[3][3];
+  quat_rot(quat, R);
+  float vw[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) vw[i] = R[i][0] * v0.v[0] + R[i][1] * v0.v[1] + R[i][2] * v0.v[2];
+  stage[0] = clip5(pos[2] - z_init);
+  stage[1] = clip5(cy * vw[0] + sy * vw[1]);
+  stage[2] = clip5(-sy * vw[0] + cy * vw[1]);
+  stage[3] = clip5(vw[2]);
+  stage[4] = clip5(roll);
+  stage[5] = clip5(pitch);
+  stage[48] = (flags & 1) ? 1.f : 0.f;
+  stage[49] = (flags & 2) ? 1.f : 0.f;
+  float t[5];
+  target_features(pos, cy, sy, p1, t1, t);
+#pragma unroll
+  for (int i = 0; i < 5; ++i) stage[50 + i] = t[i];
+  target_features(pos, cy, sy, p2, t2, t);
+#pragma unroll
+  for (int i = 0; i < 5; ++i) stage[55 + i] = t[i];
+}
 template <class Model, bool ROLLOUT>
 SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e, int side, bool valid, int lane, int lane_global,
                       int kstep, float* lds) {
@@ -435,7 +563,6 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
   constexpr int kInfoBase = kEnvsPerWave * 64;         // behind the largest staged block
   float* stage = lds + (lane >> 1) * stride;
   uint32_t* istage = reinterpret_cast<uint32_t*>(lds) + kInfoBase + (lane >> 1) * SS_INFO_WORDS;
-#define SS_OBS(i) stage[i]
   SS_WAVE_SYNC();          // the staging area is region A: every lane must be through with its contact operators
   if (valid) {
     float* Fo = P.fstate + e;
@@ -445,44 +572,16 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
       constexpr int jl = left_twin(jr);
       const int gj = side ? jl : jr;
       if (jr >= 3 || side == 0) {
-        // The observation carries POLICY coordinates (PHYSICS.md 2): ps = kPolicySign of THIS joint (left x / z joints: about the
-        // mirrored axis; knees: negative in flexion), applied to the true-world angle and to the middle of its true range (a left
-        // x / z joint's true range is (-hi, -lo) of its right twin's).  The state arrays keep angles about the +axis.
-        constexpr float midr = 0.5f * (Model::lo[jr] + Model::hi[jr]);
-        constexpr float span = Model::hi[jr] - Model::lo[jr];
-        const float ps = policy_true_sign(jr, side);
-        const float mid = (side && mirror_flips(jr)) ? -midr : midr;
         Fo[(F_Q + gj) * np] = o.qt[k];
         Fo[(F_QD + gj) * np] = o.qdt[k];
-        SS_OBS(6 + gj) = obs_angle(ps, o.qt[k], mid, span);
-        SS_OBS(27 + gj) = obs_rate(ps, o.qdt[k]);
+        stage_obs_joint<Model, k>(stage, side, o.qt[k], o.qdt[k]);
       }
     });
     if (side == 0) {
-      float R[3][3];
-      quat_rot(o.quat, R);
-      float vw[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) vw[i] = R[i][0] * o.v0.v[0] + R[i][1] * o.v0.v[1] + R[i][2] * o.v0.v[2];
-      // obs 0-5 and 48-59: the same entries as in write_obs (see there for the tests that pin the two copies together).
       // a reset leaves the identity orientation: roll = pitch = yaw = 0 exactly; otherwise the values of the final orientation
       const float r2 = o.do_reset ? 0.f : o.roll, p2 = o.do_reset ? 0.f : o.pitch;
       const float cy = o.do_reset ? 1.f : o.cyaw, sy = o.do_reset ? 0.f : o.syaw;
-      SS_OBS(0) = clip5(o.pos[2] - o.z_init);
-      SS_OBS(1) = clip5(cy * vw[0] + sy * vw[1]);
-      SS_OBS(2) = clip5(-sy * vw[0] + cy * vw[1]);
-      SS_OBS(3) = clip5(vw[2]);
-      SS_OBS(4) = clip5(r2);
-      SS_OBS(5) = clip5(p2);
-      SS_OBS(48) = (o.flags & 1) ? 1.f : 0.f;
-      SS_OBS(49) = (o.flags & 2) ? 1.f : 0.f;
-      float t[5];
-      target_features(o.pos, cy, sy, &o.tgt[0][0], &o.tgt[0][3], t);
-#pragma unroll
-      for (int i = 0; i < 5; ++i) SS_OBS(50 + i) = t[i];
-      target_features(o.pos, cy, sy, &o.tgt[1][0], &o.tgt[1][3], t);
-#pragma unroll
-      for (int i = 0; i < 5; ++i) SS_OBS(55 + i) = t[i];
+      stage_obs_base(stage, o.pos, o.quat, o.v0, o.z_init, r2, p2, cy, sy, o.flags, &o.tgt[0][0], &o.tgt[0][3], &o.tgt[1][0], &o.tgt[1][3]);
       if (io.rew) io.rew[e] = o.r;
       if (io.done) io.done[e] = o.d ? 1 : 0;
       if (packed_layout) {
@@ -566,7 +665,6 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
     }
 #endif
   }
-#undef SS_OBS
 }
 
 // The three-helper rollout kernel hands the output stage to a helper wavefront: the main wavefront leaves 14 words in the hand-off
@@ -628,6 +726,160 @@ SSD void random_actions_half(const Params& P, int e, int side, float m, uint32_t
   });
 }
 
+// Sections 6-9 of a control step by value: progress towards the target, termination, reward (PHYSICS.md 4.6-4.9)
+struct StepScore {
+  float pot_prev;                        // the potential the next step starts from
+  bool d;                                // the episode ends
+  int bad;                               // ... at the step limit
+  float r, roll, pitch, cyaw, syaw;      // reward; quat_roll_pitch_cs of quat
+};
+SSD StepScore step_score(SS_PROF_DECL const float (&pos)[3], const float (&quat)[4], const Cache& c, const float (&target_old)[3],
+                         const float (&sole)[2][3], float pot_prev, int advanced, int n, int elapsed, bool finite, float step_bonus,
+                         float e_sum, float a2, int at_limit) {
+  StepScore o;
+  // 6. progress
+  float pot = -planar_dist(target_old, pos) / kDt;
+  SS_PROFE(4);       // first use of the loaded scalars (wait for L2) + target logic (+ draw on advance)
+  float progress = pot - pot_prev;
+  o.pot_prev = advanced ? -planar_dist(c.p[1], pos) / kDt : pot;
+  // 7-8
+  float target_bonus = (n == kNumStones - 1 && planar_dist(c.p[1], pos) < 0.15f) ? 2.f : 0.f;
+  float zs = fminf(sole[0][2], sole[1][2]);
+  float tall_bonus = (pos[2] - zs > 0.7f) ? 2.f : -1.f;
+  float zlow = fminf(fminf(c.p[0][2], c.p[1][2]), c.p[2][2]);
+  bool d = (tall_bonus < 0.f) || (pos[2] < zlow + 0.3f) || !finite;
+  bool timeout = elapsed >= SS_MAX_EPISODE_STEPS;
+  o.bad = timeout ? 1 : 0;                       // TimeLimitMask (common/envs_utils.py:59-65): done at the step limit, whatever else ended it
+  o.d = d || timeout;
+  // 9. reward
+  quat_roll_pitch_cs(quat, o.roll, o.pitch, o.cyaw, o.syaw);      // of the state the step ended in (before a possible reset)
+  float posture = 0.f;
+  if (!(o.pitch > -0.2f && o.pitch < 0.4f)) posture += fabsf(o.pitch);
+  if (!(o.roll > -0.4f && o.roll < 0.4f)) posture += fabsf(o.roll);
+  float energy = (4.5f / NJ) * (e_sum / NJ) + (0.225f / NJ) * (a2 / NJ);
+  float r = progress + step_bonus + target_bonus + tall_bonus - energy - posture - 0.1f * (float)at_limit;
+  if (!finite || !finite_bits(r)) r = 0.f;
+  o.r = r;
+  SS_PROFE(5);       // progress, termination, roll / pitch, reward
+  return o;
+}
+// episode return as an unevaluated float pair (ep_ret, ep_lo): error-free two-sum of the step reward, then renormalised, so that the
+// pair carries the fp64 sum of the fp32 step rewards (Monitor.update sums Python floats, common/envs_utils.py:134)
+SSD void ep_return_add(float& ep_ret, float& ep_lo, float r) {
+  const float s = ep_ret + r, bb = s - ep_ret;
+  const float err = (ep_ret - (s - bb)) + (r - bb);
+  const float lo = ep_lo + err;
+  ep_ret = s + lo;
+  ep_lo = lo - (ep_ret - s);
+}
+
+// What the env logic of a control step (step_logic) gives back besides the env-level words it updates in place
+struct StepEnd {
+  float pos[3], quat[4];                 // the base the substeps ended in, true world
+  SV v0;
+  int flags, advanced;                   // feet in contact (bit 0: right, bit 1: left); the target moved on
+  float hd[3][2];                        // headings of the active stones, true world: meaningful after an advance only
+  bool d;                                // the episode ends
+  int bad;                               // ... at the step limit
+  float r, roll, pitch, cyaw, syaw;      // reward; quat_roll_pitch_cs of quat
+};
+// The env logic of a control step behind its substeps (PHYSICS.md 4; sections 3-9 of step_env): pair exchange of the foot reports,
+// joint sums, target logic, progress, termination, reward and the episode return, for this lane of the pair.  Env-level logic runs
+// redundantly (and identically) in both lanes in the true world.  c and the env-level words come in as loaded and go out updated.  The
+// stone of an advance comes from draw(ctr, k, p, nrm, tilt, heading, store) -> dr, the one point where a user's terrain table shows;
+// `store` marks the lane that writes the table.  LDS: the state, the actions and the headings are read, the headings rewritten on an advance.
+// The look-ahead (ss_lookahead.hpp) calls it.  step_env has sections 3-5 restated inline and calls step_score / ep_return_add itself:
+// with this function in their place the benchmarked kernel measured 1.2 of the parent's spreads slower (docs/HISTORY.md, "One
+// definition of the control step"; kept, gate failed).  tests/test_lookahead.py (host builds) and tests/test_gpu_lookahead.py hold the
+// two to the same bits on cases that reach every branch: a change of sections 3-5 is made here AND there.
+template <class Model, class Draw>
+SSD void step_logic(SS_PROF_DECL const Lds& L, int side, float m, const FootReport& fr, Cache& c, float& pot_prev, float& nn_dr,
+                    float& ep_ret, float& ep_lo, int& n, int& count, int& elapsed, uint32_t& ctr, bool store, Draw&& draw, StepEnd& o) {
+  float (&pos)[3] = o.pos, (&quat)[4] = o.quat, (&hd)[3][2] = o.hd;
+  SV& v0 = o.v0;
+  // 3-4. back to the true world; the pair shares its feet
+  get_base(L, m, pos, quat, v0);
+  elapsed += 1;
+  const float my_sole[3] = {fr.sole[0], m * fr.sole[1], fr.sole[2]};
+  float ot_sole[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ot_sole[i] = xchg(my_sole[i]);
+  const int ot_contact = xchg_i(fr.contact), ot_target = xchg_i(fr.on_target);
+  float sole[2][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { sole[0][i] = side ? ot_sole[i] : my_sole[i]; sole[1][i] = side ? my_sole[i] : ot_sole[i]; }
+  o.flags = side ? (ot_contact | (fr.contact << 1)) : (fr.contact | (ot_contact << 1));
+  const int on_target = fr.on_target | ot_target;
+  SS_PROFE(2);       // LDS state read-back, pair exchange of the foot reports
+  // partial sums over this lane's joints (the spine is counted by the right lane only)
+  float accv = 0.f, e_sum = 0.f, a2 = 0.f;
+  int at_limit = 0;
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    constexpr float mid = 0.5f * (Model::lo[jr] + Model::hi[jr]);
+    constexpr float span = Model::hi[jr] - Model::lo[jr];
+    const float q = L.s(S_Q + k), qd = L.s(S_QD + k), a = L.s(S_ACT + k);
+    const bool mine = (jr >= 3) || (side == 0);
+    accv += q + qd;
+    if (mine) {
+      e_sum += fabsf(a * (0.1f * qd));
+      a2 += a * a;
+      if (fabsf(2.f * (q - mid) / span) > 0.99f) at_limit += 1;
+    }
+  });
+  accv += pos[0] + pos[1] + pos[2] + quat[0] + quat[1] + quat[2] + quat[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) accv += v0.w[i] + v0.v[i];
+  e_sum += xchg(e_sum);
+  a2 += xchg(a2);
+  at_limit += xchg_i(at_limit);
+  const bool finite = finite_bits(accv) && (xchg_i(finite_bits(accv) ? 1 : 0) != 0);
+  SS_PROFE(3);       // joint sums (energy, limits, finiteness)
+
+  // 5. target logic
+  float target_old[3] = {c.p[1][0], c.p[1][1], c.p[1][2]};
+  float step_bonus = 0.f;
+  int advanced = 0;
+#pragma unroll
+  for (int sl = 0; sl < 3; ++sl) { hd[sl][0] = 1.f; hd[sl][1] = 0.f; }
+  if (on_target != 0) {
+    count += 1;
+    if (count == 1) {
+      float d0 = planar_dist(sole[0], target_old), d1 = planar_dist(sole[1], target_old);
+      step_bonus = 50.f * expf(-fminf(d0, d1) / 0.25f);
+    }
+    if (count >= 2 && n < kNumStones - 1) {
+      n += 1;
+      count = 0;
+      advanced = 1;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        c.p[0][i] = c.p[1][i]; c.nrm[0][i] = c.nrm[1][i];
+        c.p[1][i] = c.p[2][i]; c.nrm[1][i] = c.nrm[2][i];
+      }
+      c.tilt[0][0] = c.tilt[1][0]; c.tilt[0][1] = c.tilt[1][1];
+      c.tilt[1][0] = c.tilt[2][0]; c.tilt[1][1] = c.tilt[2][1];
+      // the headings move with the stones: slot 2 from the draw (at n = 19 it keeps the last stone's).  hd[] is the TRUE-world copy that
+      // the step kernels' write-back stores; the lane's LDS holds its own (y-mirrored) world.  LDS is read here only: a target advance
+      // is rare, a reset is not, and the write-back path must not wait for LDS
+      const float2 h1 = L.q2(kLdsHead + 1), h2 = L.q2(kLdsHead + 2);
+      hd[0][0] = h1.x; hd[0][1] = m * h1.y;
+      hd[1][0] = h2.x; hd[1][1] = m * h2.y;
+      hd[2][0] = h2.x; hd[2][1] = m * h2.y;
+      if (n + 1 <= kNumStones - 1) nn_dr = draw(ctr, n + 1, c.p[2], c.nrm[2], c.tilt[2], hd[2], store);
+      L.q2(kLdsHead + 0) = h1;
+      L.q2(kLdsHead + 1) = h2;
+      L.q2(kLdsHead + 2) = make_float2(hd[2][0], m * hd[2][1]);
+    }
+  }
+  o.advanced = advanced;
+  // 6-9. progress, termination, reward, episode return
+  const StepScore sc = step_score(SS_PROF_ARG pos, quat, c, target_old, sole, pot_prev, advanced, n, elapsed, finite, step_bonus, e_sum, a2, at_limit);
+  pot_prev = sc.pot_prev;
+  o.d = sc.d; o.bad = sc.bad; o.r = sc.r; o.roll = sc.roll; o.pitch = sc.pitch; o.cyaw = sc.cyaw; o.syaw = sc.syaw;
+  ep_return_add(ep_ret, ep_lo, sc.r);
+}
+
 // One control step, lane `lane_global` = 2*env + side (side 0: right half, true world; side 1: left half, mirrored
 // world).  PHYSICS.md section 4.  Env-level logic runs redundantly (and identically) in both lanes in the true world.
 // ROLLOUT: io.nsteps control steps in ONE launch (actions from the benchmark Philox stream at io.t, io.t+1, ...): the
@@ -649,52 +901,12 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   const size_t np = (size_t)P.npad;
   const float m = side ? -1.f : 1.f;            // y-mirror factor of this lane's world
   const Lds L{lds, lane};
-  const float* F = P.fstate + e;
-
   // Only what the substeps need is loaded before them; everything the step's epilogue needs (stone tilts,
   // counters, episode statistics) is (re)loaded afterwards from the L2-hot arrays, so that nothing sits in scratch
   // across the four substeps (those parked values were 2.2 MB of scratch write-back per launch).
-  {   // measured: merging these loads with the state loads below is slower (0.0867 vs 0.0857 ms/step)
-    Cache c0;
-    load_cache(P, e, c0);
-    float h0[3][2];
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) { h0[sl][0] = F[(F_HEAD + sl * 2) * np]; h0[sl][1] = F[(F_HEAD + sl * 2 + 1) * np]; }
-#pragma unroll
-    for (int sl = 0; sl < 3; ++sl) {
-      L.s(S_STP + sl * 3 + 0) = c0.p[sl][0]; L.s(S_STP + sl * 3 + 1) = m * c0.p[sl][1]; L.s(S_STP + sl * 3 + 2) = c0.p[sl][2];
-      L.s(S_STN + sl * 3 + 0) = c0.nrm[sl][0]; L.s(S_STN + sl * 3 + 1) = m * c0.nrm[sl][1]; L.s(S_STN + sl * 3 + 2) = c0.nrm[sl][2];
-      L.q2(kLdsHead + sl) = make_float2(h0[sl][0], m * h0[sl][1]);       // the heading in this lane's (y-mirrored) world
-    }
-  }
-
-  // 1. this lane's half of the state, mirrored for the left lane, into LDS.  All global loads are issued before the
-  //    first LDS store: written load-store-load-store the compiler waited for every load in turn (~25 exposed L2
-  //    round trips per step).
-  float gin[13], qin[NH], qdin[NH];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) gin[i] = F[(F_POS + i) * np];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) gin[3 + i] = F[(F_QUAT + i) * np];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) gin[7 + i] = F[(F_VEL + i) * np];
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = left_twin(jr);
-    const int gj = side ? jl : jr;
-    qin[k] = F[(F_Q + gj) * np];
-    qdin[k] = F[(F_QD + gj) * np];
-  });
+  // 1. stones, headings and this lane's half of the state, mirrored for the left lane, into LDS
   float ain[NH];
-  if constexpr (!RANDOM_ACT) {
-    static_for<0, NH>([&](auto Kc) {
-      constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-      constexpr int jl = left_twin(jr);
-      ain[k] = io.act[(size_t)e * NJ + (side ? jl : jr)];
-    });
-  }
-  put_base(L, m, gin, gin + 3, gin + 7, gin + 10);
-  put_joints(L, m, qin, qdin);
+  load_in<!RANDOM_ACT>(P, e, RANDOM_ACT ? nullptr : io.act + (size_t)e * NJ, side, m, L, ain);
 
   const int nsteps = ROLLOUT ? io.nsteps : 1;
 #pragma unroll 1
@@ -715,14 +927,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     }
     if (!drawn) random_actions_half(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep, [&](int k, float a) { L.s(S_ACT + k) = a; });
   } else {
-    static_for<0, NH>([&](auto Kc) {
-      constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-      const float sg = action_lane_sign(jr, m);
-      const float x = ain[k];
-      float a = fminf(fmaxf(x, -1.f), 1.f);
-      a = (x != x) ? x : a;      // a NaN action is not clipped away (fmaxf would): it ends the episode, PHYSICS.md 4.8
-      L.s(S_ACT + k) = sg * a;
-    });
+    put_actions(L, m, ain);
   }
 
   // 2. four substeps on the LDS-resident state
@@ -743,7 +948,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   SS_PROF(12);
   SS_MEMBAR();
   SS_OPAQUE(e);                                 // recompute every global address below instead of spilling 27 pointers
-  F = P.fstate + e;
+  const float* F = P.fstate + e;
   const Knobs K = *P.knobs;                     // wavefront-uniform scalar loads
   Cache c;                                      // true world
   load_cache(P, e, c);                          // (keeping these 32 words resident in LDS between the steps of the rollout kernel was
@@ -754,6 +959,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   uint32_t ctr = (uint32_t)P.istate[e + I_RNG * np];
   SS_PROFE(1);       // address arithmetic + issue of the epilogue's global loads
 
+  // Sections 3-5 are step_logic's, restated (see there: its call here failed the speed gate)
   // 3-4. back to the true world; the pair shares its feet
   float pos[3], quat[4];
   SV v0;
@@ -830,38 +1036,13 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
       L.q2(kLdsHead + 2) = make_float2(hd[2][0], m * hd[2][1]);
     }
   }
-  // 6. progress
-  float pot = -planar_dist(target_old, pos) / kDt;
-  SS_PROFE(4);       // first use of the loaded scalars (wait for L2) + target logic (+ draw on advance)
-  float progress = pot - pot_prev;
-  pot_prev = advanced ? -planar_dist(c.p[1], pos) / kDt : pot;
-  // 7-8
-  float target_bonus = (n == kNumStones - 1 && planar_dist(c.p[1], pos) < 0.15f) ? 2.f : 0.f;
-  float zs = fminf(sole[0][2], sole[1][2]);
-  float tall_bonus = (pos[2] - zs > 0.7f) ? 2.f : -1.f;
-  float zlow = fminf(fminf(c.p[0][2], c.p[1][2]), c.p[2][2]);
-  bool d = (tall_bonus < 0.f) || (pos[2] < zlow + 0.3f) || !finite;
-  bool timeout = elapsed >= SS_MAX_EPISODE_STEPS;
-  int bad = timeout ? 1 : 0;                     // TimeLimitMask (common/envs_utils.py:59-65): done at the step limit, whatever else ended it
-  d = d || timeout;
-  // 9. reward
-  float roll, pitch, cyaw, syaw;                 // of the state the step ended in (before a possible reset)
-  quat_roll_pitch_cs(quat, roll, pitch, cyaw, syaw);
-  float posture = 0.f;
-  if (!(pitch > -0.2f && pitch < 0.4f)) posture += fabsf(pitch);
-  if (!(roll > -0.4f && roll < 0.4f)) posture += fabsf(roll);
-  float energy = (4.5f / NJ) * (e_sum / NJ) + (0.225f / NJ) * (a2 / NJ);
-  float r = progress + step_bonus + target_bonus + tall_bonus - energy - posture - 0.1f * (float)at_limit;
-  if (!finite || !finite_bits(r)) r = 0.f;
-  SS_PROFE(5);       // progress, termination, roll / pitch, reward
-  {   // episode return as an unevaluated float pair (ep_ret, ep_lo): error-free two-sum of the step reward, then renormalised, so
-      // that the pair carries the fp64 sum of the fp32 step rewards (Monitor.update sums Python floats, common/envs_utils.py:134)
-    const float s = ep_ret + r, bb = s - ep_ret;
-    const float err = (ep_ret - (s - bb)) + (r - bb);
-    const float lo = ep_lo + err;
-    ep_ret = s + lo;
-    ep_lo = lo - (ep_ret - s);
-  }
+  // 6-9. progress, termination, reward, episode return
+  const StepScore sc = step_score(SS_PROF_ARG pos, quat, c, target_old, sole, pot_prev, advanced, n, elapsed, finite, step_bonus, e_sum, a2, at_limit);
+  pot_prev = sc.pot_prev;
+  const bool d = sc.d;
+  const int bad = sc.bad;
+  const float r = sc.r, roll = sc.roll, pitch = sc.pitch, cyaw = sc.cyaw, syaw = sc.syaw;
+  ep_return_add(ep_ret, ep_lo, r);
   // 10. outputs, auto-reset
   ss_info inf;
   inf.ep_ret = ep_ret;
@@ -933,13 +1114,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
       put_base(L, m, pos, quat, v0.w, v0.v);
       put_joints(L, m, qt, qdt);
     }
-    if (advanced || do_reset) {
-#pragma unroll
-      for (int sl = 0; sl < 3; ++sl) {
-        L.s(S_STP + sl * 3 + 0) = c.p[sl][0]; L.s(S_STP + sl * 3 + 1) = m * c.p[sl][1]; L.s(S_STP + sl * 3 + 2) = c.p[sl][2];
-        L.s(S_STN + sl * 3 + 0) = c.nrm[sl][0]; L.s(S_STN + sl * 3 + 1) = m * c.nrm[sl][1]; L.s(S_STN + sl * 3 + 2) = c.nrm[sl][2];
-      }
-    }
+    if (advanced || do_reset) put_stones(L, m, c);
   }
   if constexpr (kOffload) {
     L.hs(kHandOut + 0) = r;

@@ -6,10 +6,11 @@
 // row, one wavefront per workgroup, one Lds block, the dynamic state resident in LDS across the H steps (the ROLLOUT path of step_env).
 // What a control step reads or writes besides the dynamic state -- the active stones, the terrain row, the target counters, the episode
 // statistics, the RNG counter -- lives in the row's `work` words (W_* below), where the step kernel has the env's own arrays: loaded
-// after the substeps, stored by the right lane, so that nothing is held in registers across substep().  The epilogue of step_env
-// (ss_kernels.hpp sections 3-10) is inline there and is RESTATED in look_row, with the reset branch left out, and so are draw_stone's
-// lines around the terrain table (draw_stone_row: the table is the row's private one); tests/test_gpu_lookahead.py holds every output
-// bit for bit to ss_step's, which pins the restatement.
+// after the substeps, stored by the right lane, so that nothing is held in registers across substep().  The env logic of a control step
+// is one definition with step_env's (ss_kernels.hpp): load_in, put_actions, step_logic (sections 3-9; step_env keeps sections 3-5 inline
+// and the reset branch, and calls step_score / ep_return_add of sections 6-9 as step_logic does), put_stones and stage_obs_joint /
+// stage_obs_base.  What look_row adds is where the words live: the draw of an advance reads and writes the row's private terrain table
+// (sample_stone and stone_after around it are draw_stone's).  tests/test_gpu_lookahead.py holds every output bit for bit to ss_step's.
 //
 // Every function is SSD (host and device): tests/host/lookahead_host.cpp runs the same code on the CPU, the 64 lanes as threads.  The
 // kernel and its launcher are in ss_lookahead.hip.
@@ -35,12 +36,10 @@ enum { W_TERR = 0, W_STONE = 120, W_POT = 144, W_ZINIT, W_EPRET, W_EPLO, W_NNDR,
 static_assert(W_END <= SS_LOOK_WORK && SS_LOOK_WORK % 4 == 0, "a work row holds the branch's words, rows stay 16-byte aligned");
 static_assert(SS_LOOK_MAX_STEPS == SS_MAX_EPISODE_STEPS, "no branch outlives an episode");
 
-// Two words that a lane keeps across the substeps, in item 39 of LDS region A (free: ss_forces.hpp, kLdsNote): 1 + the step the branch
-// finished in (0: it has not), and which of the float4 this lane copies out per step belong to rows that may be written (copy_obs).
+// Two words that a lane keeps across the substeps, in kLdsNote (ss_kernels.hpp): 1 + the step the branch finished in (0: it has not),
+// and which of the float4 this lane copies out per step belong to rows that may be written (copy_obs).
 // The Lds block has no room for the observation row a finished branch repeats, and a second block would cost the fourth workgroup of a
 // CU: the row is read back from obs[k, f, :], which this wavefront wrote in step f.
-constexpr int kLdsNote = kLdsHead + 3;
-static_assert(kLdsNote < kSlotsA * 2, "the note is inside region A");
 constexpr int kRow4 = SS_OBS_DIM / 4;                          // float4 per observation row
 constexpr int kCopyIters = (kEnvsPerWave * kRow4 + kWave - 1) / kWave;
 static_assert(kEnvsPerWave * SS_OBS_DIM <= kEnvsPerWave * 64, "the staged rows stay in front of region A's headings, as in emit_outputs");
@@ -55,56 +54,6 @@ SSD int f2i(float x) { return __builtin_bit_cast(int, x); }
 #else
 #define SS_LOOK_ALL(pred) (false && (pred))
 #endif
-
-// draw_stone (ss_kernels.hpp) on the branch's own terrain table Tw [120]: the same draws from the env's counter, global id, curriculum
-// and probability grid, the predecessor read from Tw (whose provisional stones are written out: 0.75 (k - 1), 0, 0, 0 are the words
-// draw_stone takes for a stone that is not stored), the new stone written to Tw by the lane that stores
-SSD float draw_stone_row(const Params& P, const Knobs& K, int e, uint32_t& ctr, int k, float* Tw, float out_p[3], float out_n[3],
-                         float out_t[2], float out_h[2], bool store) {
-  uint32_t r[4];
-  env_block(P, e, ctr, r);
-  int cell = sample_cell(P, K, e, u01(r[0]));
-  float ratio = (float)K.curriculum / 5.0f;
-  float dr = 0.65f + u01(r[1]) * (0.6f * ratio);
-  float tilt = 15.0f * kDeg * ratio;
-  float xt = (2.f * u01(r[2]) - 1.f) * tilt, yt = (2.f * u01(r[3]) - 1.f) * tilt;
-  float yaw = yaw_sample(cell / SS_GRID), pitch = pitch_sample(cell % SS_GRID);
-  const int kk = k < 1 ? 1 : (k > kNumStones - 1 ? kNumStones - 1 : k);      // (1 <= k <= 19 for every state ss_step accepts)
-  const float* prev = Tw + (kk - 1) * 6;
-  float px = prev[0], py = prev[1], pz = prev[2];
-  float phi = prev[3] + yaw;
-  float sp, cp, sph, cph;
-  sincosf(pitch, &sp, &cp);
-  sincosf(phi, &sph, &cph);
-  place_stone(px, py, pz, dr, cp, sp, cph, sph, out_p);
-  out_t[0] = xt; out_t[1] = yt;
-  out_h[0] = cph; out_h[1] = sph;
-  stone_normal(phi, xt, yt, out_n);
-  if (store) {
-    float* o = Tw + kk * 6;
-    o[0] = out_p[0]; o[1] = out_p[1]; o[2] = out_p[2];
-    o[3] = phi; o[4] = xt; o[5] = yt;
-  }
-  return dr;
-}
-
-// the clipped, lane-signed actions of one step into the lane's LDS column (the action clip of step_env)
-SSD void put_actions(const float* act_row, int side, float m, const Lds& L) {
-  float ain[NH];
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = left_twin(jr);
-    ain[k] = act_row[side ? jl : jr];
-  });
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    const float sg = action_lane_sign(jr, m);
-    const float x = ain[k];
-    float a = fminf(fmaxf(x, -1.f), 1.f);
-    a = (x != x) ? x : a;      // a NaN action stays a NaN: it ends the episode (PHYSICS.md 4.8)
-    L.s(S_ACT + k) = sg * a;
-  });
-}
 
 // The private copy of env e in the row's work words.  The two lanes of the row share the terrain table.
 SSD void init_work(const Params& P, int e, int side, float* W) {
@@ -163,7 +112,8 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
   const float m_ = side ? -1.f : 1.f;                        // y-mirror factor of this lane's world
   const int row0 = (lane_global - lane) >> 1;                // first row of this wavefront
   const Lds L{lds, lane};
-  frc::load_row(P, e, act + (size_t)row * (size_t)H * NJ, side, m_, L);
+  float ain[NH];
+  load_in<false>(P, e, nullptr, side, m_, L, ain);            // (every step loads its own actions)
   if (own) init_work(P, e, side, out.work + (size_t)row * SS_LOOK_WORK);
   {
     uint32_t okmask = 0;
@@ -186,7 +136,8 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
     int d_out = 1;
     // wavefront-uniform: nothing of this wavefront is left to compute, the frozen rows below are all that remains
     if (!SS_LOOK_ALL(fin != 0 || !valid)) {
-      put_actions(act + ((size_t)row * (size_t)H + (size_t)s) * NJ, side, m_, L);
+      load_actions(act + ((size_t)row * (size_t)H + (size_t)s) * NJ, side, ain);
+      put_actions(L, m_, ain);
       const float power = P.knobs->power;
       FootReport fr;
 #if defined(SS_PROFILE_PHASES) && defined(__HIP_DEVICE_COMPILE__)
@@ -219,117 +170,35 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
       int n = f2i(W[W_N]), count = f2i(W[W_COUNT]), elapsed = f2i(W[W_ELAPSED]);
       uint32_t ctr = (uint32_t)f2i(W[W_RNG]);
 
-      // ---- step_env sections 3-10, restated (ss_kernels.hpp); no reset branch: a branch never resets ----
-      // 3-4. back to the true world; the pair shares its feet
-      float pos[3], quat[4];
-      SV v0;
-      get_base(L, m_, pos, quat, v0);
-      elapsed += 1;
-      const float my_sole[3] = {fr.sole[0], m_ * fr.sole[1], fr.sole[2]};
-      float ot_sole[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) ot_sole[i] = xchg(my_sole[i]);
-      const int ot_contact = xchg_i(fr.contact), ot_target = xchg_i(fr.on_target);
-      float sole[2][3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { sole[0][i] = side ? ot_sole[i] : my_sole[i]; sole[1][i] = side ? my_sole[i] : ot_sole[i]; }
-      const int flags = side ? (ot_contact | (fr.contact << 1)) : (fr.contact | (ot_contact << 1));
-      const int on_target = fr.on_target | ot_target;
-      // partial sums over this lane's joints (the spine is counted by the right lane only)
-      float accv = 0.f, e_sum = 0.f, a2 = 0.f;
-      int at_limit = 0;
-      static_for<0, NH>([&](auto Kc) {
-        constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-        constexpr float mid = 0.5f * (Model::lo[jr] + Model::hi[jr]);
-        constexpr float span = Model::hi[jr] - Model::lo[jr];
-        const float q = L.s(S_Q + k), qd = L.s(S_QD + k), a = L.s(S_ACT + k);
-        const bool mine = (jr >= 3) || (side == 0);
-        accv += q + qd;
-        if (mine) {
-          e_sum += fabsf(a * (0.1f * qd));
-          a2 += a * a;
-          if (fabsf(2.f * (q - mid) / span) > 0.99f) at_limit += 1;
-        }
-      });
-      accv += pos[0] + pos[1] + pos[2] + quat[0] + quat[1] + quat[2] + quat[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) accv += v0.w[i] + v0.v[i];
-      e_sum += xchg(e_sum);
-      a2 += xchg(a2);
-      at_limit += xchg_i(at_limit);
-      const bool finite = finite_bits(accv) && (xchg_i(finite_bits(accv) ? 1 : 0) != 0);
-
-      // 5. target logic
-      float target_old[3] = {c.p[1][0], c.p[1][1], c.p[1][2]};
-      float step_bonus = 0.f;
-      int advanced = 0;
-      if (on_target != 0) {
-        count += 1;
-        if (count == 1) {
-          float d0 = planar_dist(sole[0], target_old), d1 = planar_dist(sole[1], target_old);
-          step_bonus = 50.f * expf(-fminf(d0, d1) / 0.25f);
-        }
-        if (count >= 2 && n < kNumStones - 1) {
-          n += 1;
-          count = 0;
-          advanced = 1;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            c.p[0][i] = c.p[1][i]; c.nrm[0][i] = c.nrm[1][i];
-            c.p[1][i] = c.p[2][i]; c.nrm[1][i] = c.nrm[2][i];
-          }
-          c.tilt[0][0] = c.tilt[1][0]; c.tilt[0][1] = c.tilt[1][1];
-          c.tilt[1][0] = c.tilt[2][0]; c.tilt[1][1] = c.tilt[2][1];
-          // the headings move with the stones: slot 2 from the draw (at n = 19 it keeps the last stone's); they live in LDS only
-          const float2 h1 = L.q2(kLdsHead + 1), h2 = L.q2(kLdsHead + 2);
-          float h_new[2] = {h2.x, m_ * h2.y};
-          if (n + 1 <= kNumStones - 1)
-            nn_dr = draw_stone_row(P, K, e, ctr, n + 1, W + W_TERR, c.p[2], c.nrm[2], c.tilt[2], h_new, store);
-          L.q2(kLdsHead + 0) = h1;
-          L.q2(kLdsHead + 1) = h2;
-          L.q2(kLdsHead + 2) = make_float2(h_new[0], m_ * h_new[1]);
-        }
-      }
-      // 6. progress
-      float pot = -planar_dist(target_old, pos) / kDt;
-      float progress = pot - pot_prev;
-      pot_prev = advanced ? -planar_dist(c.p[1], pos) / kDt : pot;
-      // 7-8
-      float target_bonus = (n == kNumStones - 1 && planar_dist(c.p[1], pos) < 0.15f) ? 2.f : 0.f;
-      float zs = fminf(sole[0][2], sole[1][2]);
-      float tall_bonus = (pos[2] - zs > 0.7f) ? 2.f : -1.f;
-      float zlow = fminf(fminf(c.p[0][2], c.p[1][2]), c.p[2][2]);
-      bool d = (tall_bonus < 0.f) || (pos[2] < zlow + 0.3f) || !finite;
-      bool timeout = elapsed >= SS_MAX_EPISODE_STEPS;
-      d = d || timeout;
-      // 9. reward
-      float roll, pitch, cyaw, syaw;
-      quat_roll_pitch_cs(quat, roll, pitch, cyaw, syaw);
-      float posture = 0.f;
-      if (!(pitch > -0.2f && pitch < 0.4f)) posture += fabsf(pitch);
-      if (!(roll > -0.4f && roll < 0.4f)) posture += fabsf(roll);
-      float energy = (4.5f / NJ) * (e_sum / NJ) + (0.225f / NJ) * (a2 / NJ);
-      float r = progress + step_bonus + target_bonus + tall_bonus - energy - posture - 0.1f * (float)at_limit;
-      if (!finite || !finite_bits(r)) r = 0.f;
-      {   // episode return as an unevaluated float pair: error-free two-sum of the step reward, then renormalised
-        const float sm = ep_ret + r, bb = sm - ep_ret;
-        const float err = (ep_ret - (sm - bb)) + (r - bb);
-        const float lo = ep_lo + err;
-        ep_ret = sm + lo;
-        ep_lo = lo - (ep_ret - sm);
-      }
+      // step_env sections 3-9 (step_logic); no reset branch: a branch never resets.  The stone of an advance is read from and written
+      // to the branch's own terrain table, whose provisional stones are written out (0.75 (k - 1), 0, 0, 0 are the words draw_stone
+      // takes for a stone that is not stored)
+      StepEnd se;
+      step_logic<Model>(SS_PROF_ARG L, side, m_, fr, c, pot_prev, nn_dr, ep_ret, ep_lo, n, count, elapsed, ctr, store,
+                        [&](uint32_t& ct, int k, float* p, float* nrm, float* tilt, float* h, bool st) {
+                          float xt, yt, yaw, pitch;
+                          const float dr = sample_stone(P, K, e, ct, xt, yt, yaw, pitch);
+                          const int kk = k < 1 ? 1 : (k > kNumStones - 1 ? kNumStones - 1 : k);      // (1 <= k <= 19 for every state ss_step accepts)
+                          const float* prev = W + W_TERR + (kk - 1) * 6;
+                          const float phi = prev[3] + yaw;
+                          stone_after(prev[0], prev[1], prev[2], phi, dr, pitch, xt, yt, p, nrm, tilt, h);
+                          if (st) {
+                            float* o = W + W_TERR + kk * 6;
+                            o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+                            o[3] = phi; o[4] = xt; o[5] = yt;
+                          }
+                          return dr;
+                        }, se);
+      const float (&pos)[3] = se.pos, (&quat)[4] = se.quat;
+      const SV& v0 = se.v0;
+      const int flags = se.flags, advanced = se.advanced;
+      const bool d = se.d;
+      const float r = se.r;
       // joint values of this lane in the true world
       float qt[NH], qdt[NH];
       get_joints(L, m_, qt, qdt);
       // the LDS copy of the stones is what the next step's substeps read (the ROLLOUT path of step_env)
-      if (advanced) {
-#pragma unroll
-        for (int sl = 0; sl < 3; ++sl) {
-          L.s(S_STP + sl * 3 + 0) = c.p[sl][0]; L.s(S_STP + sl * 3 + 1) = m_ * c.p[sl][1]; L.s(S_STP + sl * 3 + 2) = c.p[sl][2];
-          L.s(S_STN + sl * 3 + 0) = c.nrm[sl][0]; L.s(S_STN + sl * 3 + 1) = m_ * c.nrm[sl][1]; L.s(S_STN + sl * 3 + 2) = c.nrm[sl][2];
-        }
-      }
-      // ---- end of the restated lines ----
+      if (advanced) put_stones(L, m_, c);
 
       if (live) {
         r_out = r;
@@ -340,43 +209,12 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
         SS_WAVE_SYNC();          // the staging area is region A: every lane must be through with its contact operators
         if (live) {
           float* stage = lds + (lane >> 1) * SS_OBS_DIM;
-#define SS_OBS(i, v) stage[i] = (v)
           static_for<0, NH>([&](auto Kc) {
-            constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-            constexpr int jl = left_twin(jr);
-            const int gj = side ? jl : jr;
-            if (jr >= 3 || side == 0) {
-              constexpr float midr = 0.5f * (Model::lo[jr] + Model::hi[jr]);
-              constexpr float span = Model::hi[jr] - Model::lo[jr];
-              const float ps = policy_true_sign(jr, side);
-              const float mid = (side && mirror_flips(jr)) ? -midr : midr;
-              SS_OBS(6 + gj, obs_angle(ps, qt[k], mid, span));
-              SS_OBS(27 + gj, obs_rate(ps, qdt[k]));
-            }
+            constexpr int k = decltype(Kc)::value;
+            if (kHalf[k] >= 3 || side == 0) stage_obs_joint<Model, k>(stage, side, qt[k], qdt[k]);
           });
-          if (side == 0) {
-            float R[3][3];
-            quat_rot(quat, R);
-            float vw[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) vw[i] = R[i][0] * v0.v[0] + R[i][1] * v0.v[1] + R[i][2] * v0.v[2];
-            SS_OBS(0, clip5(pos[2] - z_init));
-            SS_OBS(1, clip5(cyaw * vw[0] + syaw * vw[1]));
-            SS_OBS(2, clip5(-syaw * vw[0] + cyaw * vw[1]));
-            SS_OBS(3, clip5(vw[2]));
-            SS_OBS(4, clip5(roll));
-            SS_OBS(5, clip5(pitch));
-            SS_OBS(48, (flags & 1) ? 1.f : 0.f);
-            SS_OBS(49, (flags & 2) ? 1.f : 0.f);
-            float t[5];
-            target_features(pos, cyaw, syaw, c.p[1], c.tilt[1], t);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) SS_OBS(50 + i, t[i]);
-            target_features(pos, cyaw, syaw, c.p[2], c.tilt[2], t);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) SS_OBS(55 + i, t[i]);
-          }
-#undef SS_OBS
+          if (side == 0)
+            stage_obs_base(stage, pos, quat, v0, z_init, se.roll, se.pitch, se.cyaw, se.syaw, flags, c.p[1], c.tilt[1], c.p[2], c.tilt[2]);
         }
       }
       // the dynamic state the branch ends in: the finishing step's, or the last step's
