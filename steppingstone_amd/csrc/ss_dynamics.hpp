@@ -129,6 +129,19 @@ static_assert(S_END <= (kLdsSlots - kSlotsA) * 4, "LDS scalar region overflow");
 // wavefronts: 192 - 205 of 256 AGPRs), in the lane's LDS scalars otherwise (the plain and the one-helper rollout kernels sit at
 // 252 - 255 AGPRs and would spill 20 - 40 B per lane; 13 ds_write + 13 ds_read per substep instead).  Values are the same either way.
 constexpr bool warm_in_lds(int helpers) { return helpers < 3; }
+// The joint angles of an env's NEXT reset (PHYSICS.md 7: q0 + noise from the Philox blocks at the env's counter, clamped) are a function
+// of (seed, env id, counter) alone, and the counter moves only when the env resets or draws a stone: in the three-helper K-step kernel a
+// helper wavefront draws them ahead of time, in its idle window behind barrier #3 of a control step's first substep, and leaves the
+// lane's twelve angles, in the lane's own world (what put_joints would store), in S_WLAM .. S_WLAM + 11, which that kernel does not use
+// (its warm-start impulses live in registers).  The main wavefront's reset copies them instead of drawing; a lane whose counter moved
+// in the very step it resets in (a stone drawn on a target advance) draws inline as before.  Same functions, same order, same bits.
+// Device builds only (step_env); every other kernel keeps the inline draw and is the code it was.
+constexpr bool reset_pose_offload(int helpers, bool kstep) { return helpers >= 3 && kstep; }
+constexpr int S_POSE = S_WLAM;
+static_assert(!(reset_pose_offload(0, true) && warm_in_lds(0)) && !(reset_pose_offload(1, true) && warm_in_lds(1)) &&
+              !(reset_pose_offload(2, true) && warm_in_lds(2)) && !(reset_pose_offload(3, true) && warm_in_lds(3)),
+              "the reset pose lives where the warm-start impulses would: only a kernel that keeps those in registers has the words to spare");
+static_assert(S_POSE + NH <= S_POS, "twelve words");
 
 // the half-tree: global (right-side) joint ids, spine first
 constexpr int kHalf[NH] = {0, 1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 16};

@@ -354,6 +354,29 @@ SSD void env_reset(const Params& P, int e, Dyn& s, Cache& c, uint32_t& ctr, floa
   nn_dr = 0.75f;
   pot = -planar_dist(c.p[1], s.pos) / kDt;
 }
+// The reset pose of this lane's half of env e at Philox counter ctr, in the lane's OWN world: write(k, angle) gets what put_joints
+// stores to S_Q + k after a reset (reset_pose_offload() in ss_dynamics.hpp).  The six blocks of the reset noise are drawn three per lane
+// of the pair and exchanged, as in step_env's reset branch: every lane of a pair calls this together.
+template <class Model, class Write>
+SSD void reset_pose_half(const Params& P, int e, int side, float m, uint32_t ctr, Write&& write) {
+  uint32_t rr[6][4], c3 = ctr + (side ? 3u : 0u), mine[3][4];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) env_block(P, e, c3, mine[b]);
+#pragma unroll
+  for (int b = 0; b < 3; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t other = xchg_u32(mine[b][i]);
+      rr[b][i] = side ? other : mine[b][i];
+      rr[3 + b][i] = side ? mine[b][i] : other;
+    }
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    constexpr int jl = left_twin(jr);
+    const float qt = side ? reset_angle<Model, jl>(rr) : reset_angle<Model, jr>(rr);      // true world, as step_env's
+    write(k, mirror_sign(jr, m) * qt);
+  });
+}
 
 // Peer-to-peer all-gather fused into the step kernel (multi-GPU, ss_step_packed_peers): every workgroup stores its rows of
 // the packed block straight into each peer's gather buffer (xGMI stores into fine-grained memory) instead of a local
@@ -676,6 +699,10 @@ SSD void emit_outputs(const Params& P, const StepIO& io, const StepOut& o, int e
 constexpr bool out_offload(int helpers, bool rollout) { return rollout && helpers >= 3; }
 constexpr int kHandOut = kHandDet, kHandOut2 = kHandFloats;     // 13 + 2 words
 static_assert(kHandOut2 + 2 <= kHandSlots * 4, "hand-off region");
+// kHandOut2 + 1, the second spare word: the env's Philox counter as the control step leaves it, for the helper that draws the reset pose
+// ahead of time (reset_pose_offload() in ss_dynamics.hpp; the three-helper K-step kernel, the only one that writes or reads the word)
+constexpr int kHandCtr = kHandOut2 + 1;
+static_assert(kHandCtr < kHandRows3, "below the rows' own words");
 #if !defined(SS_HOST_HARNESS)
 template <class Model, bool ROLLOUT>
 __device__ __forceinline__ void emit_from_handoff(const Params& P, const StepIO& io, const Lds& L, int lane, int lane_global, int kstep,
@@ -895,6 +922,13 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
 #else
       false;
 #endif
+  constexpr bool kPose =               // reset pose drawn ahead of time by a helper wavefront (reset_pose_offload() in ss_dynamics.hpp)
+#if defined(__HIP_DEVICE_COMPILE__)
+      reset_pose_offload(HELPERS, ROLLOUT);
+#else
+      false;
+#endif
+  static_assert(!kPose || kOffload, "the pose's helper and the counter's hand-off word are the output stage's kernel's");
   const int e_raw = lane_global >> 1, side = lane_global & 1;
   const bool valid = e_raw < P.n;
   int e = valid ? e_raw : P.n - 1;
@@ -957,6 +991,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   float ep_ret = F[F_EPRET * np], ep_lo = F[F_EPRET_LO * np], nn_dr = F[F_NNDR * np];
   int n = P.istate[e + I_N * np], count = P.istate[e + I_COUNT * np], elapsed = P.istate[e + I_ELAPSED * np];
   uint32_t ctr = (uint32_t)P.istate[e + I_RNG * np];
+  const uint32_t ctr_in = ctr;                  // (kPose: the counter the helper drew the reset pose at)
   SS_PROFE(1);       // address arithmetic + issue of the epilogue's global loads
 
   // Sections 3-5 are step_logic's, restated (see there: its call here failed the speed gate)
@@ -1054,6 +1089,8 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   const bool do_reset = d && K.auto_reset;
   SS_PROFE(6);
   uint32_t rr[6][4];
+  // kPose: the pose in S_POSE was drawn at ctr_in; a lane that drew a stone in this very step has moved on and draws inline (below)
+  const bool pose_stale = kPose && do_reset && ctr != ctr_in;
   if (do_reset) {
     // PHYSICS.md section 7: provisional terrain (prov_from = 0: no table writes), standing pose, joint noise from 6 Philox blocks
     if (valid && side == 0) P.istate[e + I_PROV * np] = 0;
@@ -1070,7 +1107,9 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     // the six Philox blocks of the reset noise: three per lane of the pair, exchanged (round 6: both lanes used to draw all six --
     // 300 more instructions on every control step in which ANY of the wavefront's 32 envs resets, i.e. on 3 steps of 4 under random
     // actions).  Integer-exact: the words are the ones env_block() would have produced.
-    {
+    if constexpr (kPose) {             // a helper wavefront drew them (reset_pose_half): no Philox here
+      ctr += 6u;
+    } else {
       uint32_t c3 = ctr + (side ? 3u : 0u), mine[3][4];
 #pragma unroll
       for (int b = 0; b < 3; ++b) env_block(P, e, c3, mine[b]);
@@ -1093,18 +1132,20 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   // joint values of this lane in the TRUE world (after the optional reset).  Read per joint on purpose: get_joints() in the else
   // branch of one `if (do_reset)` is the same values and about 2 900 moved instructions in every step / rollout kernel
   float qt[NH], qdt[NH];
-  static_for<0, NH>([&](auto Kc) {
-    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr int jl = left_twin(jr);
-    const float sg = mirror_sign(jr, m);
-    if (do_reset) {
-      qt[k] = side ? reset_angle<Model, jl>(rr) : reset_angle<Model, jr>(rr);
-      qdt[k] = 0.f;
-    } else {
-      qt[k] = sg * L.s(S_Q + k);
-      qdt[k] = sg * L.s(S_QD + k);
-    }
-  });
+  if constexpr (!kPose) {
+    static_for<0, NH>([&](auto Kc) {
+      constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+      constexpr int jl = left_twin(jr);
+      const float sg = mirror_sign(jr, m);
+      if (do_reset) {
+        qt[k] = side ? reset_angle<Model, jl>(rr) : reset_angle<Model, jr>(rr);
+        qdt[k] = 0.f;
+      } else {
+        qt[k] = sg * L.s(S_Q + k);
+        qdt[k] = sg * L.s(S_QD + k);
+      }
+    });
+  }
   // 11. output stage (emit_outputs): inline, or on a helper wavefront in the three-helper rollout kernel
   SS_PROFE(8);       // joint values of the next state
   SS_FUZZ(0x62u);
@@ -1112,8 +1153,33 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     // the LDS copy of the state is what comes next (the next step, a helper's output stage): refresh what the env logic changed
     if (do_reset) {
       put_base(L, m, pos, quat, v0.w, v0.v);
-      put_joints(L, m, qt, qdt);
+      if constexpr (kPose) {
+        // The joints: the helper's twelve words as they are, and the zero rates as put_joints stores them, mirror_sign x 0 -- the left
+        // lane's mirrored joints hold -0, which the output stage's get_joints turns back into the +0 of the true world.  Written as
+        // bits: -fno-signed-zeros must not choose the sign
+        float qp[NH];
+#pragma unroll
+        for (int k = 0; k < NH; ++k) qp[k] = L.s(S_POSE + k);
+        const float zm = __builtin_bit_cast(float, side ? 0x80000000u : 0u);
+        static_for<0, NH>([&](auto Kc) {
+          constexpr int k = decltype(Kc)::value;
+          L.s(S_Q + k) = qp[k];
+          L.s(S_QD + k) = mirror_flips(kHalf[k]) ? zm : 0.f;
+        });
+      } else {
+        put_joints(L, m, qt, qdt);
+      }
     }
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (kPose) {
+      // the inline draw, for the lanes whose counter moved behind the helper's back: target advance with a stone drawn AND reset in one
+      // step.  Wavefront-level branch: the common path never executes it.  Both lanes of a pair take it together (the env logic is theirs
+      // in common), so the exchange inside has its partner
+      if (__any(pose_stale)) {
+        if (pose_stale) reset_pose_half<Model>(P, e, side, m, ctr - 6u, [&](int k, float q) { L.s(S_Q + k) = q; });
+      }
+    }
+#endif
     if (advanced || do_reset) put_stones(L, m, c);
   }
   if constexpr (kOffload) {
@@ -1123,6 +1189,7 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
     const int bits = (d ? 1 : 0) | (inf.bad_transition << 1) | (inf.update_terrain << 2) | ((do_reset ? 1 : 0) << 3) | (flags << 4) |
                      (inf.steps_reached << 8) | ((int)inf.ep_len << 16);
     L.hs(kHandOut2 + 0) = __builtin_bit_cast(float, bits);
+    if constexpr (kPose) L.hs(kHandCtr) = __builtin_bit_cast(float, ctr);
 #pragma unroll
     for (int i = 0; i < 3; ++i) { L.hs(kHandOut + 3 + i) = c.p[1][i]; L.hs(kHandOut + 8 + i) = c.p[2][i]; }
 #pragma unroll
@@ -1218,10 +1285,20 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
     const int lane_global = blockIdx.x * kWave + lane, side = lane_global & 1;
     const int e = min(lane_global >> 1, P.n - 1);
     const float m = side ? -1.f : 1.f;
+    // The reset pose (reset_pose_offload() in ss_dynamics.hpp) is this helper's, behind barrier #3 of a control step's first substep, where
+    // every helper idles until the main wavefront is through its PGS.  The counter it draws at: in the launch's first step the one in
+    // HBM -- the state is resident before the launch and the main wavefront stores a counter only in its epilogue, behind barrier #0 of
+    // the second substep, which this wavefront reaches with the load consumed --, afterwards the word the previous step's epilogue left
+    // in the hand-off region (barriers #0 .. #3 of this step lie between that store and this read; the next store follows barrier #0 of
+    // the next substep).  It draws again only when some lane's counter has moved (a reset, a stone drawn): ctr_pose is what S_POSE holds.
+    constexpr int kPoseHelper = 0;
+    uint32_t ctr_pose = 0u;
+    if constexpr (reset_pose_offload(HELPERS, true))
+      if (wave - 1 == kPoseHelper) ctr_pose = (uint32_t)P.istate[e + I_RNG * (size_t)P.npad];
 #pragma unroll 1
     for (int kstep = 0; kstep < io.nsteps; ++kstep)
 #pragma unroll 1
-      for (int k = 0; k < kNumSubsteps; ++k)
+      for (int k = 0; k < kNumSubsteps; ++k) {
         helper_substep<Model, HELPERS, 4>(wave - 1, L, [&](int helper) {
           if (k != 0) return;
           SS_FUZZ(0x80u + helper);
@@ -1234,6 +1311,17 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
           // the previous control step's outputs
           if (out_offload(HELPERS, true) && helper == kEmitHelper && kstep > 0) emit_from_handoff<Model, true>(P, io, L, lane, lane_global, kstep - 1, lds);
         });
+        if constexpr (reset_pose_offload(HELPERS, true)) {
+          if (k == 0 && wave - 1 == kPoseHelper) {
+            SS_FUZZ(0xA0u);
+            const uint32_t ctr_now = kstep == 0 ? ctr_pose : __builtin_bit_cast(uint32_t, L.hs(kHandCtr));
+            if (kstep == 0 || __any(ctr_now != ctr_pose)) {      // wavefront-uniform: every lane of a pair is in the exchange
+              ctr_pose = ctr_now;
+              reset_pose_half<Model>(P, e, side, m, ctr_now, [&](int j, float q) { L.s(S_POSE + j) = q; });
+            }
+          }
+        }
+      }
     if constexpr (out_offload(HELPERS, true)) {
       __syncthreads();                 // the last step's results are in the hand-off region
       SS_FUZZ(0x90u + wave);

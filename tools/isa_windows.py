@@ -113,7 +113,7 @@ def main():
     body = text[a:b + 1]
     res = {}
     for l in text[b:]:
-        m = re.match(r"^; (NumVgprs|NumAgprs|ScratchSize|codeLenInByte): (\d+)", l)
+        m = re.match(r"^; (NumVgprs|NumAgprs|ScratchSize|LDSByteSize): (\d+)", l)
         if m and m.group(1) not in res:
             res[m.group(1)] = int(m.group(2))
         if len(res) == 4:
@@ -150,6 +150,14 @@ def main():
     print("  %-22s %9d %9d %9d" % ("all", tot(once), tot(sweep), tot(ex)))
     print("  executed per substep: %d; of them without a value (v_mov reg + v_mov lit + s_mov lit + agpr moves + s_nop): %d"
           % (tot(ex), ex["v_mov reg"] + ex["v_mov lit"] + ex["s_mov lit"] + ex["agpr moves"] + ex["s_nop"]))
+    # the control step's epilogue: the basic blocks of the main wavefront's control-step loop (the substep loop's parent) that the layout
+    # has behind the substep loop's last one.  A STATIC count (its branches -- reset, target advance -- are not all taken in a step): for
+    # A/B tables of the same code, not for clocks
+    last = max(i for i, (lab, com, _) in enumerate(bl) if lab == head or re.search(r"(Header=|Parent Loop )%s Depth=2" % head, com))
+    outer = re.search(r"Parent Loop (BB\d+_\d+) Depth=1", next(com for lab, com, _ in bl if lab == head)).group(1)
+    behind = count([l for _, com, ls in bl[last + 1:] if re.search(r"Header=%s Depth=1" % outer, com) for l in ls])
+    print("main wavefront, behind the substep loop (the control step's epilogue, static): %d VALU, %d LDS, %d global memory, %d in all"
+          % (sum(behind[k] for k in VALU), behind["LDS"], behind["global memory"], tot(behind)))
 
 
 if __name__ == "__main__":
