@@ -142,6 +142,37 @@ static_assert(!(reset_pose_offload(0, true) && warm_in_lds(0)) && !(reset_pose_o
               !(reset_pose_offload(2, true) && warm_in_lds(2)) && !(reset_pose_offload(3, true) && warm_in_lds(3)),
               "the reset pose lives where the warm-start impulses would: only a kernel that keeps those in registers has the words to spare");
 static_assert(S_POSE + NH <= S_POS, "twelve words");
+// The tail of a substep behind the base's velocity change dv0 (chol6_solve_neg at the end of the contact response) is three pieces that
+// do not depend on each other: the spine + leg down-sweep, which needs the impulses ul[] and stays on the main wavefront; the arm
+// down-sweep with the arm joints' integration (the arms hang on the base and carry no contact impulse: dv0, their four records, their free
+// rates and angles are all it reads); the base's integration (dv0, the free twist v0f, the quaternion).  In the three-helper K-step kernel,
+// whose main wavefront's instruction stream bounds the step, helper 1 takes the arms and helper 2 the base behind a sixth barrier, #3r,
+// which the main wavefront reaches with dv0 in the hand-off region; the helpers idle there anyway.  What crosses, in words that are dead
+// at that moment (the kernel's LDS does not grow):
+//   the four arm records        kHandArm: the rows' first 36 words, written by the main wavefront at the end of the #2 -> #3 window, behind
+//                               its own fetch of the rows (same wavefront: program order); helper 0 writes rows again behind the next #1
+//   dv0, v0f                    kHandDv0 / kHandV0f: twelve of the output stage's words, which the emitting helper reads between #0b and #1
+//                               of a step's first substep and the main wavefront's epilogue writes: free from that #1 to the epilogue.
+//                               dv0 is written by every lane (zeros without a contact: the wavefront may have skipped the solve)
+//   the arm joints' free rates  their own S_QD words: nobody reads those between pass 1's loads and the next #0
+//   "the pair is in contact"    formed by the helper as substep() forms it, from the flags word of the detection
+//   the base's rotation         formed by the helper from S_QUAT with quat_rot, as substep() does
+// Behind the control step's last substep one more barrier lets the epilogue read what the helpers stored; between substeps the next #0
+// does.  Same functions, same expressions, same bits (tests/test_gpu_limb_tail_bits.py).  Device builds only; every other kernel keeps
+// the tail inline and is the code it was.  The two pieces have a switch each for A/B builds (-DSS_ARM_TAIL=0, -DSS_BASE_TAIL=0).
+#ifndef SS_ARM_TAIL
+#define SS_ARM_TAIL 1
+#endif
+#ifndef SS_BASE_TAIL
+#define SS_BASE_TAIL 1
+#endif
+constexpr bool arm_tail_offload(int helpers, bool kstep) { return SS_ARM_TAIL != 0 && helpers >= 3 && kstep; }
+constexpr bool base_tail_offload(int helpers, bool kstep) { return SS_BASE_TAIL != 0 && helpers >= 3 && kstep; }
+constexpr bool limb_tail_offload(int helpers, bool kstep) { return arm_tail_offload(helpers, kstep) || base_tail_offload(helpers, kstep); }
+constexpr int kHandArm = kHandRows3, kHandDv0 = kHandDet, kHandV0f = kHandDv0 + 6;
+constexpr int kArmHelper = 1, kBaseHelper = 2;
+static_assert(kHandArm + 4 * kRecWords <= kHandRows3 + 36, "the arm records fit the rows' directions");
+static_assert(kHandV0f + 6 <= kHandDet + 13, "dv0 and v0f stay below the detection's flags word and the sole");
 
 // the half-tree: global (right-side) joint ids, spine first
 constexpr int kHalf[NH] = {0, 1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 16};
@@ -278,16 +309,18 @@ struct JointCache {
 };
 constexpr int half_pos(int j) { return j <= 7 ? j : j - 5; }   // 13..16 -> 8..11
 // the hand-off region's layout of joint record k (u stays with the main wavefront) and of the base factor: one writer, one reader
-SSD void put_rec(const Lds& L, int k, const JRec& r) {
-  L.hs(kHandJc + k * kRecWords + 0) = r.cs; L.hs(kHandJc + k * kRecWords + 1) = r.sn; L.hs(kHandJc + k * kRecWords + 2) = r.Dinv;
+SSD void put_rec_at(const Lds& L, int w, const JRec& r) {      // at hand-off word w
+  L.hs(w + 0) = r.cs; L.hs(w + 1) = r.sn; L.hs(w + 2) = r.Dinv;
 #pragma unroll
-  for (int m = 0; m < 3; ++m) { L.hs(kHandJc + k * kRecWords + 3 + m) = r.Uw[m]; L.hs(kHandJc + k * kRecWords + 6 + m) = r.Uv[m]; }
+  for (int m = 0; m < 3; ++m) { L.hs(w + 3 + m) = r.Uw[m]; L.hs(w + 6 + m) = r.Uv[m]; }
 }
-SSD void get_rec(const Lds& L, int k, JRec& r) {
-  r.cs = L.hs(kHandJc + k * kRecWords + 0); r.sn = L.hs(kHandJc + k * kRecWords + 1); r.Dinv = L.hs(kHandJc + k * kRecWords + 2);
+SSD void get_rec_at(const Lds& L, int w, JRec& r) {
+  r.cs = L.hs(w + 0); r.sn = L.hs(w + 1); r.Dinv = L.hs(w + 2);
 #pragma unroll
-  for (int m = 0; m < 3; ++m) { r.Uw[m] = L.hs(kHandJc + k * kRecWords + 3 + m); r.Uv[m] = L.hs(kHandJc + k * kRecWords + 6 + m); }
+  for (int m = 0; m < 3; ++m) { r.Uw[m] = L.hs(w + 3 + m); r.Uv[m] = L.hs(w + 6 + m); }
 }
+SSD void put_rec(const Lds& L, int k, const JRec& r) { put_rec_at(L, kHandJc + k * kRecWords, r); }
+SSD void get_rec(const Lds& L, int k, JRec& r) { get_rec_at(L, kHandJc + k * kRecWords, r); }
 SSD void put_chol(const Lds& L, const Chol6& c) {
 #pragma unroll
   for (int m = 0; m < 15; ++m) L.hs(kHandL0 + m) = c.l[m];
@@ -753,7 +786,83 @@ SSD SVT<T> aba_acc(const JRecT<T>& r, const T& qd, const SVT<T>& aprev, const SV
   return a;
 }
 
+// The pieces of a substep's tail that do not need the contact impulses (limb_tail_offload() above): one definition each, called inline by
+// substep() and, in the three-helper K-step kernel, by the helper wavefronts.
+// the arm joints 13..16 follow the base's velocity change dv0 (no bias: ul[] is not read)
+template <class Model>
+SSD void arm_response(const JointCache& jc, const SV& dv0, float* dqd) {
+  SV d = dv0;
+  static_for<13, 17>([&](auto Jc) {
+    constexpr int j = decltype(Jc)::value;
+    d = imp_down<Model, j, false>(jc, nullptr, d, &dqd[half_pos(j)]);
+  });
+}
+// semi-implicit Euler of the joint at position k of the half-tree: free rate qf + contact response dqd, the angle qq; state back to LDS
+SSD void integrate_joint(const Lds& L, int k, float qf, float dqd, float qq) {
+  constexpr float h = kH;
+  float qd = qf + dqd;
+  L.s(S_QD + k) = qd;
+  L.s(S_Q + k) = qq + h * qd;
+}
+// the base: twist, position and orientation (quat / Rb: the pose the substep began with), state back to LDS
+SSD void integrate_base(const Lds& L, const SV& v0f, const SV& dv0, const float (&Rb)[3][3], const float (&quat)[4]) {
+  constexpr float h = kH;
+  SV v0n;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { v0n.w[i] = v0f.w[i] + dv0.w[i]; v0n.v[i] = v0f.v[i] + dv0.v[i]; }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { L.s(S_VW + i) = v0n.w[i]; L.s(S_VV + i) = v0n.v[i]; }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    L.s(S_POS + r) += h * (Rb[r][0] * v0n.v[0] + Rb[r][1] * v0n.v[1] + Rb[r][2] * v0n.v[2]);
+  {
+    float qw = quat[0], qx = quat[1], qy = quat[2], qz = quat[3];
+    float ox = v0n.w[0], oy = v0n.w[1], oz = v0n.w[2], hh = 0.5f * h;
+    float nw = qw + hh * (-qx * ox - qy * oy - qz * oz);
+    float nx = qx + hh * (qw * ox + qy * oz - qz * oy);
+    float ny = qy + hh * (qw * oy - qx * oz + qz * ox);
+    float nz = qz + hh * (qw * oz + qx * oy - qy * ox);
+    float inv = SS_RSQRT(nw * nw + nx * nx + ny * ny + nz * nz);
+    L.s(S_QUAT) = nw * inv; L.s(S_QUAT + 1) = nx * inv; L.s(S_QUAT + 2) = ny * inv; L.s(S_QUAT + 3) = nz * inv;
+  }
+}
+
 #ifndef SS_HOST_HARNESS
+// The helpers' side of limb_tail_offload(), behind barrier #3r (rollout_kernel_helped).  Helper kArmHelper: the arm records, dv0, the
+// free rates and the angles from LDS, the response for the lanes whose pair is in contact (the others add 0.f, as substep() does), the
+// arm joints' new state.
+template <class Model>
+__device__ __forceinline__ void helper_arm_tail(const Lds& L) {
+  const int active = __builtin_bit_cast(int, L.hs(kHandDet + 13)) & 15;
+  JointCache jc;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) get_rec_at(L, kHandArm + i * kRecWords, jc.r[8 + i]);
+  SV dv0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { dv0.w[i] = L.hs(kHandDv0 + i); dv0.v[i] = L.hs(kHandDv0 + 3 + i); }
+  float qf[NH], qq[NH], dqd[NH];
+#pragma unroll
+  for (int k = 8; k < NH; ++k) { qf[k] = L.s(S_QD + k); qq[k] = L.s(S_Q + k); dqd[k] = 0.f; }
+  SS_MEMBAR();
+  const bool in_contact = (active | xchg_i(active)) != 0;
+  if (in_contact) arm_response<Model>(jc, dv0, dqd);
+#pragma unroll
+  for (int k = 8; k < NH; ++k) integrate_joint(L, k, qf[k], dqd[k], qq[k]);
+}
+// Helper kBaseHelper: the base's pose, dv0 and v0f from LDS, the base's new state.
+__device__ __forceinline__ void helper_base_tail(const Lds& L) {
+  float quat[4] = {L.s(S_QUAT), L.s(S_QUAT + 1), L.s(S_QUAT + 2), L.s(S_QUAT + 3)};
+  SV v0f, dv0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    dv0.w[i] = L.hs(kHandDv0 + i); dv0.v[i] = L.hs(kHandDv0 + 3 + i);
+    v0f.w[i] = L.hs(kHandV0f + i); v0f.v[i] = L.hs(kHandV0f + 3 + i);
+  }
+  SS_MEMBAR();
+  float Rb[3][3];
+  quat_rot(quat, Rb);
+  integrate_base(L, v0f, dv0, Rb, quat);
+}
 // Helper wavefronts of the small-batch variant (one workgroup = main wavefront + HELPERS helpers, five barriers per substep):
 //   #0 state of the substep is in LDS         helpers: cos / sin of the joint angles -> LDS (main: joint torques)
 //   #0b                                        helper 0: forward kinematics, contact detection -> LDS
@@ -947,6 +1056,12 @@ SSD void joint_tau(float power, ssf2 q, ssf2 qd, ssf2 act, ssf2& tau, ssf2& Dadd
 template <class Model, int HELPERS = 0, bool KSTEP = false>      // KSTEP: inside a K-step (rollout) kernel
 SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& wm) {
   constexpr float h = kH;
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool kArmTail = arm_tail_offload(HELPERS, KSTEP), kBaseTail = base_tail_offload(HELPERS, KSTEP);   // helpers 1 and 2 behind #3r
+#else
+  constexpr bool kArmTail = false, kBaseTail = false;
+#endif
+  constexpr bool kTail = kArmTail || kBaseTail;
   JointCache jc;
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (HELPERS > 0) { __syncthreads(); SS_FUZZ(0x1Fu); }   // #0: the state of this substep is in LDS (helper 0: kinematics + detection)
@@ -1385,8 +1500,16 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
         for (int k = 0; k < 4; ++k) rB[k] = L.hs(kHandRows3 + 36 + k);
       }
   };
-  auto solve = [&]() {              // y = Lambda w, PGS, response of the whole tree
-      float ul[NH];
+  float ul[NH];                      // the bias impulses of the spine + leg joints (the response's way up leaves them for its way down)
+  auto respond_down = [&]() {       // from dv0 down the tree: spine + leg, then the arms (unless a helper wavefront has them)
+      SV d = dv0;
+      static_for<0, 8>([&](auto Jc) {
+        constexpr int j = decltype(Jc)::value;
+        d = imp_down<Model, j, true>(jc, ul, d, &dqd[half_pos(j)]);
+      });
+      if constexpr (!kArmTail) arm_response<Model>(jc, dv0, dqd);
+  };
+  auto solve = [&]() {              // y = Lambda w, PGS, response of the whole tree (kTail: as far as dv0)
       float wlam_prev[4][3];           // the previous substep's impulses
       int wkey_prev = 0;
       auto load_warm = [&]() {
@@ -1583,16 +1706,7 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
         for (int i = 0; i < 3; ++i) { p.w[i] += po.w[i]; p.v[i] += po.v[i]; }
         static_rfor<2, 0>([&](auto Jc) { p = imp_up<Model, decltype(Jc)::value>(jc, ul, p); });
         dv0 = chol6_solve_neg(jc.L0, p);
-        SV d = dv0;
-        static_for<0, 8>([&](auto Jc) {
-          constexpr int j = decltype(Jc)::value;
-          d = imp_down<Model, j, true>(jc, ul, d, &dqd[half_pos(j)]);
-        });
-        d = dv0;
-        static_for<13, 17>([&](auto Jc) {
-          constexpr int j = decltype(Jc)::value;
-          d = imp_down<Model, j, false>(jc, ul, d, &dqd[half_pos(j)]);
-        });
+        if constexpr (!kTail) respond_down();
       }
   };
   if (!in_contact) {                 // no contact in this substep: nothing to start the next one from
@@ -1619,47 +1733,52 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
   } else {
     if (in_contact) rows_free();
 #if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (kArmTail) {        // the rows are fetched: the arm records take their place, the arm joints' free rates their S_QD words
+#pragma unroll
+      for (int i = 0; i < 4; ++i) put_rec_at(L, kHandArm + i * kRecWords, jc.r[8 + i]);
+#pragma unroll
+      for (int k = 8; k < NH; ++k) L.s(S_QD + k) = SS_QDF(k);
+    }
+    if constexpr (kBaseTail) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { L.hs(kHandV0f + i) = v0f.w[i]; L.hs(kHandV0f + 3 + i) = v0f.v[i]; }
+    }
     SS_PROF(8);
     __syncthreads();                 // #3: the helper wavefront(s) have written C, T and Lambda_own
     SS_PROF(7);                      // (tuning builds, helper variants: the wait at barrier #3)
     SS_FUZZ(0x5Fu);
 #endif
     if (in_contact) solve();
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (kTail) {
+      // every lane: a wavefront without a contact skipped the solve and leaves zeros.  The barrier stands outside the lane-divergent
+      // branches, where every wavefront meets it
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { L.hs(kHandDv0 + i) = dv0.w[i]; L.hs(kHandDv0 + 3 + i) = dv0.v[i]; }
+      __builtin_amdgcn_sched_barrier(0);
+      SS_PROF(10);
+      __syncthreads();               // #3r: dv0 is in the hand-off region (helper 1: the arms, helper 2: the base)
+      SS_PROF(6);                    // (tuning builds: the wait at barrier #3r, in the slot of the detection's read-back)
+      SS_FUZZ(0xBFu);
+      __builtin_amdgcn_sched_barrier(0);
+      if (in_contact) respond_down();
+    }
+#endif
   }
   SS_MEMBAR();
   SS_PROF(10);
 
   // ---- integrate (semi-implicit Euler), state back to LDS
   {
+    constexpr int kMine = kArmTail ? 8 : NH;     // (kArmTail: the arm joints are helper 1's)
     float qf[NH], qq[NH];
 #pragma unroll
-    for (int k = 0; k < NH; ++k) { qf[k] = SS_QDF(k); qq[k] = L.s(S_Q + k); }   // (q kept in registers to here: slower)
+    for (int k = 0; k < kMine; ++k) { qf[k] = SS_QDF(k); qq[k] = L.s(S_Q + k); }   // (q kept in registers to here: slower)
     SS_MEMBAR();
 #pragma unroll
-    for (int k = 0; k < NH; ++k) {
-      float qd = qf[k] + dqd[k];
-      L.s(S_QD + k) = qd;
-      L.s(S_Q + k) = qq[k] + h * qd;
-    }
+    for (int k = 0; k < kMine; ++k) integrate_joint(L, k, qf[k], dqd[k], qq[k]);
   }
-  SV v0n;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { v0n.w[i] = v0f.w[i] + dv0.w[i]; v0n.v[i] = v0f.v[i] + dv0.v[i]; }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { L.s(S_VW + i) = v0n.w[i]; L.s(S_VV + i) = v0n.v[i]; }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    L.s(S_POS + r) += h * (Rb[r][0] * v0n.v[0] + Rb[r][1] * v0n.v[1] + Rb[r][2] * v0n.v[2]);
-  {
-    float qw = quat[0], qx = quat[1], qy = quat[2], qz = quat[3];
-    float ox = v0n.w[0], oy = v0n.w[1], oz = v0n.w[2], hh = 0.5f * h;
-    float nw = qw + hh * (-qx * ox - qy * oy - qz * oz);
-    float nx = qx + hh * (qw * ox + qy * oz - qz * oy);
-    float ny = qy + hh * (qw * oy - qx * oz + qz * ox);
-    float nz = qz + hh * (qw * oz + qx * oy - qy * ox);
-    float inv = SS_RSQRT(nw * nw + nx * nx + ny * ny + nz * nz);
-    L.s(S_QUAT) = nw * inv; L.s(S_QUAT + 1) = nx * inv; L.s(S_QUAT + 2) = ny * inv; L.s(S_QUAT + 3) = nz * inv;
-  }
+  if constexpr (!kBaseTail) integrate_base(L, v0f, dv0, Rb, quat);     // (kBaseTail: helper 2's)
   SS_MEMBAR();
   SS_PROF(11);
 }

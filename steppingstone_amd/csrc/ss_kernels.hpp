@@ -978,6 +978,13 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   if constexpr (warm_in_lds(HELPERS)) L.s(S_WKEY) = 0.f;
 #pragma unroll 1
   for (int k = 0; k < kNumSubsteps; ++k) substep<Model, HELPERS, ROLLOUT>(SS_PROF_ARG power, fr, L, wm);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (limb_tail_offload(HELPERS, ROLLOUT)) {   // helpers 1 and 2 integrate the arm joints and the base of the last substep
+    SS_PROF(11);
+    __syncthreads();                 // their stores are in LDS: the epilogue reads S_Q, S_QD and the base
+    SS_FUZZ(0xCFu);
+  }
+#endif
   SS_FUZZ(0x61u);
   SS_PROF(12);
   SS_MEMBAR();
@@ -1319,6 +1326,21 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
               ctr_pose = ctr_now;
               reset_pose_half<Model>(P, e, side, m, ctr_now, [&](int j, float q) { L.s(S_POSE + j) = q; });
             }
+          }
+        }
+        // The substep's tail behind dv0 (limb_tail_offload() in ss_dynamics.hpp): every helper meets #3r, helper 1 takes the arms and
+        // helper 2 the base while the main wavefront sweeps down its spine and leg.  The next substep's #0 orders their stores; behind a
+        // control step's last substep the main wavefront's epilogue reads them, behind one more barrier
+        if constexpr (limb_tail_offload(HELPERS, true)) {
+          __syncthreads();             // #3r: dv0 is in the hand-off region
+          SS_FUZZ(0xB0u + (wave - 1));
+          if constexpr (arm_tail_offload(HELPERS, true))
+            if (wave - 1 == kArmHelper) helper_arm_tail<Model>(L);
+          if constexpr (base_tail_offload(HELPERS, true))
+            if (wave - 1 == kBaseHelper) helper_base_tail(L);
+          if (k == kNumSubsteps - 1) {
+            __syncthreads();           // the state the control step's epilogue reads is in LDS
+            SS_FUZZ(0xC0u + (wave - 1));
           }
         }
       }

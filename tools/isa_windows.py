@@ -4,7 +4,10 @@ section 5.1's window table and section 9's "what is left".  The compiler lays th
 (#0->#0b cos/sin, #0b->#1 kinematics / detection / rows / bias / extra, #1->#2 operators part A, #2->#3 part B) | main wavefront
 (#0->#0b joint torques, #0b->#1 pass 1 + leg/arm half of pass 2, #1->#2 spine + base factorisation, #2->#3 pass 3 + foot twist,
 #3->end: rows y = Lambda w, the PGS (its sweep loop appears ONCE here and runs kPgsIters - 1 times, the last sweep is straight-line
-code behind it), response of the tree, integration and the control step's epilogue) | tail.
+code behind it), response of the tree, integration and the control step's epilogue) | tail.  With limb_tail_offload() (ss_dynamics.hpp) the
+table has two windows more per side, split at every s_barrier like the rest: helpers #3->#3r (the reset pose), #3r->the barrier in front of
+the epilogue (helper 1: arm down-sweep and arm joints, helper 2: the base's integration, both in the one window of the layout); main
+wavefront #3->#3r (rows y = Lambda w, PGS, response up to dv0), #3r->epilogue barrier (spine + leg down-sweep, eight joints' integration).
 
 Below the window table: the instructions the main wavefront EXECUTES per substep, by class -- every line of its substep loop once
 (every branch inside it taken as falling through: the contact branch is always taken at the benchmark's workload) and the lines of
