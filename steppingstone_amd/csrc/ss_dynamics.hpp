@@ -173,6 +173,23 @@ constexpr int kHandArm = kHandRows3, kHandDv0 = kHandDet, kHandV0f = kHandDv0 + 
 constexpr int kArmHelper = 1, kBaseHelper = 2;
 static_assert(kHandArm + 4 * kRecWords <= kHandRows3 + 36, "the arm records fit the rows' directions");
 static_assert(kHandV0f + 6 <= kHandDet + 13, "dv0 and v0f stay below the detection's flags word and the sole");
+// The explicit torques and implicit diagonals of the spine joints 0..2 (joint_tau) are consumed only behind barrier #1, by joint_scalar in
+// the spine window.  In the three-helper K-step kernel helper 1, whose bias job in front of #1 already reads the spine's rates, evaluates
+// them there with the very joint_tau the main wavefront called in front of #0b, and leaves tau[3], Dadd[3] in six words of Lambda_own's
+// place that cos / sin do not cover: Lc is written behind #2 and read by the main wavefront behind #3, cos / sin take its first 24 words
+// between #0 and #0b, so words 24..29 of it are dead from #0 to #2 in every substep (the output stage and the action draw of a step's
+// first substep have their own words, kHandDet.. and kHandAct..).  The main wavefront reads them behind #1 and skips the three calls.
+// Same function, same bits (tests/test_gpu_spine_tau_bits.py).  Device builds only; every other kernel keeps the calls and is the code it
+// was.  -DSS_SPINE_TAU=0 for A/B builds.
+#ifndef SS_SPINE_TAU
+#define SS_SPINE_TAU 1
+#endif
+constexpr bool spine_tau_offload(int helpers, bool kstep) { return SS_SPINE_TAU != 0 && helpers >= 3 && kstep; }
+constexpr int kHandTau = kHandCs + 2 * NH, kTauHelper = 1;      // tau of joints 0..2, then Dadd of joints 0..2
+static_assert(kHandTau >= kHandCs + 2 * NH && kHandTau + 6 <= kHandLc + 36 && kHandLc + 36 <= kHandDet,
+              "the spine torques lie behind cos / sin, inside Lambda_own's 36 words, below the detection's");
+static_assert(hand_far(kHandTau) && hand_far_offset(kHandTau + 5) <= hand_far_offset(hand_last_word(3)), "far words inside the three-helper allocation");
+static_assert(bias_offload(3) && kTauHelper == 1, "the spine torques ride on helper 1's bias job");
 
 // the half-tree: global (right-side) joint ids, spine first
 constexpr int kHalf[NH] = {0, 1, 2, 3, 4, 5, 6, 7, 13, 14, 15, 16};
@@ -875,8 +892,12 @@ __device__ __forceinline__ void helper_base_tail(const Lds& L) {
 // (helper 1) and emits the previous step's outputs (the last helper, three-helper variant).
 // CS_PER: how many of the 12 cos / sin pairs each evaluating helper takes (three helpers).  6: helpers 1 and 2, helper 0 idles; 4: all
 // three.  A property of the kernel, measured per kernel (step_kernel_helped: 6, rollout_kernel_helped: 4; see ss_rollout3.hip).
-template <class Model, int HELPERS, int CS_PER, class Extra>
-__device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&& extra) {
+// SPINE_TAU (spine_tau_offload() above; the K-step kernel passes its `power`): helper 1 also evaluates the spine joints' torques in front of #1.
+template <class Model, int J>
+SSD void joint_tau(float power, float q, float qd, float act, float& tau, float& Dadd);
+template <class Model, int HELPERS, int CS_PER, bool SPINE_TAU = false, class Extra>
+__device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&& extra, float power = 0.f) {
+  static_assert(!SPINE_TAU || (bias_offload(HELPERS) && cs_offload(HELPERS)), "the spine torques ride on helper 1's bias job");
   static_assert(CS_PER == 4 || CS_PER == 6, "the 12 cos / sin pairs go to three helpers (4 each) or to two (6 each)");
   __syncthreads();                                   // #0
   SS_FUZZ(0x10u + helper);
@@ -938,7 +959,21 @@ __device__ __forceinline__ void helper_substep(int helper, const Lds& L, Extra&&
       float qd3[3], cs3[3], sn3[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) { qd3[k] = L.s(S_QD + k); cs3[k] = L.hs(kHandCs + k); sn3[k] = L.hs(kHandCs + NH + k); }
+      float q3[3], act3[3];
+      if constexpr (SPINE_TAU) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { q3[k] = L.s(S_Q + k); act3[k] = L.s(S_ACT + k); }
+      }
       SS_MEMBAR();
+      if constexpr (SPINE_TAU) {       // the spine joints' torques and implicit diagonals, for the main wavefront's spine window
+        static_assert(kHalf[0] == 0 && kHalf[1] == 1 && kHalf[2] == 2, "the spine joints stand first in the half-tree");
+        static_for<0, 3>([&](auto Jc) {
+          constexpr int j = decltype(Jc)::value;
+          float tau, Dadd;
+          joint_tau<Model, j>(power, q3[j], qd3[j], act3[j], tau, Dadd);
+          L.hs(kHandTau + j) = tau; L.hs(kHandTau + 3 + j) = Dadd;
+        });
+      }
       SV prev = v0;
       static_for<0, 3>([&](auto Jc) {
         constexpr int j = decltype(Jc)::value, bd = j + 1;
@@ -1062,6 +1097,11 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
   constexpr bool kArmTail = false, kBaseTail = false;
 #endif
   constexpr bool kTail = kArmTail || kBaseTail;
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool kSpineTau = spine_tau_offload(HELPERS, KSTEP);     // helper 1 evaluates the spine joints' torques in front of #1
+#else
+  constexpr bool kSpineTau = false;
+#endif
   JointCache jc;
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (HELPERS > 0) { __syncthreads(); SS_FUZZ(0x1Fu); }   // #0: the state of this substep is in LDS (helper 0: kinematics + detection)
@@ -1082,7 +1122,9 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
   if constexpr (cs_offload(HELPERS) && HELPERS > 0) {
     static_for<0, NH>([&](auto Kc) {
       constexpr int k = decltype(Kc)::value;
-      if constexpr (torques_paired(HELPERS, KSTEP) && k >= 3 && k != 7) {
+      if constexpr (kSpineTau && k < 3) {
+        // helper 1's, read behind #1
+      } else if constexpr (torques_paired(HELPERS, KSTEP) && k >= 3 && k != 7) {
         if constexpr (k < 7) {           // joints (3 + i, 13 + i) at the leg half's turn: one formula on the pair
           ssf2 tau2, dadd2;
           ss::joint_tau<Model, kHalf[k], kHalf[k + 5]>(power, pkv(q_all[k], q_all[k + 5]), pkv(qd_all[k], qd_all[k + 5]),
@@ -1309,6 +1351,10 @@ SSD void substep(SS_PROF_DECL float power, FootReport& fr, const Lds& L, Warm& w
         SS_PROF(14);                   // (tuning builds: the main wavefront's wait at barrier #1)
         SS_FUZZ(0x3Fu);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (kSpineTau) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { tau_pre[k] = L.hs(kHandTau + k); dadd_pre[k] = L.hs(kHandTau + 3 + k); }
+        }
       }
 #endif
       // I2 / p2: leg half in pelvis coordinates, arm half in torso coordinates.  Add the partner lane's limbs

@@ -205,6 +205,17 @@ SSD float clip5(float x) { return fminf(fmaxf(x, -5.f), 5.f); }
 SSD float obs_angle(float ps, float q, float mid, float span) { return clip5(2.f * (ps * q - ps * mid) / span); }
 SSD float obs_rate(float ps, float qd) { return clip5(0.1f * (ps * qd)); }
 
+// "Joint J is at its limit" (PHYSICS.md 4: the normalised angle beyond 0.99), one definition for step_env and step_logic.  The division
+// stays: a compare of fabsf(q - mid) with the smallest float at which this form is true gives the same answer for every q (the division
+// is correctly rounded, hence monotone) and takes 146 VALU instructions off the control step's epilogue, but the three-helper K-step
+// kernel measured slower with it (docs/HISTORY.md "Spine torques on helper 1").
+template <class Model, int J>
+SSD bool at_joint_limit(float q) {
+  constexpr float mid = 0.5f * (Model::lo[J] + Model::hi[J]);
+  constexpr float span = Model::hi[J] - Model::lo[J];
+  return fabsf(2.f * (q - mid) / span) > 0.99f;
+}
+
 // observation (PHYSICS.md section 5) written row-major to obs[60].  The base / contact / target entries (obs 0-5, 48-59) are
 // written a second time in emit_outputs, on the lane-pair layout of the step kernels (merging the two moves the instructions of the
 // benchmarked kernel); tests/test_gpu_env_control.py::test_reset_of_finished_envs_equals_auto_reset and
@@ -843,15 +854,13 @@ SSD void step_logic(SS_PROF_DECL const Lds& L, int side, float m, const FootRepo
   int at_limit = 0;
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr float mid = 0.5f * (Model::lo[jr] + Model::hi[jr]);
-    constexpr float span = Model::hi[jr] - Model::lo[jr];
     const float q = L.s(S_Q + k), qd = L.s(S_QD + k), a = L.s(S_ACT + k);
     const bool mine = (jr >= 3) || (side == 0);
     accv += q + qd;
     if (mine) {
       e_sum += fabsf(a * (0.1f * qd));
       a2 += a * a;
-      if (fabsf(2.f * (q - mid) / span) > 0.99f) at_limit += 1;
+      if (at_joint_limit<Model, jr>(q)) at_limit += 1;
     }
   });
   accv += pos[0] + pos[1] + pos[2] + quat[0] + quat[1] + quat[2] + quat[3];
@@ -1023,15 +1032,13 @@ SSD void step_env(const Params& P, const StepIO& io, int lane_global, int lane, 
   int at_limit = 0;
   static_for<0, NH>([&](auto Kc) {
     constexpr int k = decltype(Kc)::value, jr = kHalf[k];
-    constexpr float mid = 0.5f * (Model::lo[jr] + Model::hi[jr]);
-    constexpr float span = Model::hi[jr] - Model::lo[jr];
     const float q = L.s(S_Q + k), qd = L.s(S_QD + k), a = L.s(S_ACT + k);
     const bool mine = (jr >= 3) || (side == 0);
     accv += q + qd;
     if (mine) {
       e_sum += fabsf(a * (0.1f * qd));
       a2 += a * a;
-      if (fabsf(2.f * (q - mid) / span) > 0.99f) at_limit += 1;
+      if (at_joint_limit<Model, jr>(q)) at_limit += 1;
     }
   });
   accv += pos[0] + pos[1] + pos[2] + quat[0] + quat[1] + quat[2] + quat[3];
@@ -1299,6 +1306,7 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
     // in the hand-off region (barriers #0 .. #3 of this step lie between that store and this read; the next store follows barrier #0 of
     // the next substep).  It draws again only when some lane's counter has moved (a reset, a stone drawn): ctr_pose is what S_POSE holds.
     constexpr int kPoseHelper = 0;
+    const float power = spine_tau_offload(HELPERS, true) ? P.knobs->power : 0.f;     // as step_env reads it, for helper 1's joint_tau
     uint32_t ctr_pose = 0u;
     if constexpr (reset_pose_offload(HELPERS, true))
       if (wave - 1 == kPoseHelper) ctr_pose = (uint32_t)P.istate[e + I_RNG * (size_t)P.npad];
@@ -1306,7 +1314,7 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
     for (int kstep = 0; kstep < io.nsteps; ++kstep)
 #pragma unroll 1
       for (int k = 0; k < kNumSubsteps; ++k) {
-        helper_substep<Model, HELPERS, 4>(wave - 1, L, [&](int helper) {
+        helper_substep<Model, HELPERS, 4, spine_tau_offload(HELPERS, true)>(wave - 1, L, [&](int helper) {
           if (k != 0) return;
           SS_FUZZ(0x80u + helper);
           // the next control step's actions, while the main wavefront is in pass 1 / 2 of this step's first substep
@@ -1317,7 +1325,7 @@ __global__ __launch_bounds__(kWave * (1 + HELPERS), 1) void rollout_kernel_helpe
             random_actions_half(P, e, side, m, (uint32_t)io.t + (uint32_t)kstep + 1u, [&](int j, float a) { L.hs(kHandAct + j) = a; });
           // the previous control step's outputs
           if (out_offload(HELPERS, true) && helper == kEmitHelper && kstep > 0) emit_from_handoff<Model, true>(P, io, L, lane, lane_global, kstep - 1, lds);
-        });
+        }, power);
         if constexpr (reset_pose_offload(HELPERS, true)) {
           if (k == 0 && wave - 1 == kPoseHelper) {
             SS_FUZZ(0xA0u);
