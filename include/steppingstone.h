@@ -41,7 +41,8 @@ extern "C" {
                             * existing layout or meaning changed, so a version-4 binding keeps working.  So was the kinematic
                             * readout (ss_kinematics), the force readout (ss_step_forces) and the equation-of-motion readout
                             * (ss_eom), the impulse (ss_push), the one addition that writes: velocities only, and the look-ahead
-                            * (ss_lookahead), which writes nothing of an env. */
+                            * (ss_lookahead), which writes nothing of an env, with its from-states form (ss_lookahead_states) and
+                            * the observation of state rows (ss_get_obs_states). */
 #define SS_MAX_EPISODE_STEPS 1000
 
 typedef enum { SS_WALKER3D = 0, SS_MIKE = 1 } ss_kind;   /* ids: README.md:27,31 of the reference */
@@ -346,6 +347,35 @@ int ss_push(ss_env* env, const int32_t* env_ids, int32_t m, const int32_t* body,
 #define SS_LOOK_WORK 160                /* f32 words of workspace per row */
 int ss_lookahead(ss_env* env, const int32_t* env_ids, int32_t m, int32_t horizon, const float* act,
                  float* obs, float* rew, uint8_t* done, float* final_state, float* work, void* stream);
+
+/* Look-ahead from caller-supplied states (docs/PHYSICS.md "Branches from caller-supplied states"); added under version 4 (nothing
+ * existing moved).  Row k is a branch of env env_ids[k] that starts from states[k, :] instead of that env's current state: its obs, rew,
+ * done and final_state rows are bit for bit what ss_lookahead writes for a row with that id and those actions after ss_set_state_envs
+ * has put states[k] into env env_ids[k].  NOTHING of the env changes: no state word, no terrain row, no RNG counter, no knob.  The env
+ * supplies what a state row does not carry: its global id (the Philox key of the stones drawn on an advance), its row of a per-env
+ * probability grid, the curriculum level, the shared grid and ss_set_power.  The RNG counter is the row's (words 62 and 63).  The row is
+ * read as ss_set_state reads it: the integer words through (int), all 20 terrain rows as stored, the active stones' normals and headings
+ * from the terrain words of stones n-1, n, n+1 (n = word 59; the three indices are clamped into [0, 19], which changes nothing for a
+ * state ss_step accepts, 1 <= n <= 19: no row, whatever its 186 words hold, makes the call read or write outside that row's own
+ * buffers), the quaternion as given.
+ *   states: DEVICE [m, SS_STATE_DIM] f32, the ss_get_state layout, required when m > 0; 4-byte aligned (final_state + k * SS_STATE_DIM of
+ *     an earlier call can be passed as it is).  Only read.
+ *   env_ids, horizon, act, obs, rew, done, final_state, work: as in ss_lookahead, word for word -- frozen rows behind a first done, the
+ *     time limit, a NaN action, repeated ids (now each with its own state), env_ids == NULL (envs 0..m-1, needs m == N), an id outside
+ *     [0, N) (skipped: nothing of an env is read, no output row of it is written), m == 0 (does nothing), the 16-byte alignment of obs,
+ *     rew, final_state and work, SS_LOOK_WORK words of workspace per row.
+ * Ordered on `stream`, never synchronises the host, allocates nothing, can be captured into a graph.  Bad host arguments return
+ * SS_ERR_INVALID and launch nothing.  A row's bits depend on its id, its state row, the knobs and its actions alone. */
+int ss_lookahead_states(ss_env* env, const int32_t* env_ids, int32_t m, const float* states, int32_t horizon,
+                        const float* act, float* obs, float* rew, uint8_t* done, float* final_state, float* work,
+                        void* stream);
+
+/* Observation of state rows: obs[k, :] (DEVICE [m, 60] f32) is bit for bit ss_get_obs's row of an env after ss_set_state of states[k, :]
+ * (DEVICE [m, SS_STATE_DIM] f32) -- the observation at the root of a branch, which ss_lookahead* never returns, and what relabelling a
+ * logged state needs.  Added under version 4.  It only reads `states`; the handle supplies the robot kind; an observation depends on no
+ * id and no knob.  m >= 0 (0: nothing happens); states and obs are required when m > 0, 4-byte aligned.  Ordered on `stream`, never
+ * synchronises the host, allocates nothing, can be captured into a graph.  Bad host arguments return SS_ERR_INVALID and launch nothing. */
+int ss_get_obs_states(ss_env* env, int32_t m, const float* states, float* obs, void* stream);
 
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.

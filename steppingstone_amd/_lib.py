@@ -22,6 +22,7 @@ SYMBOLS = [
     "ss_step_packed_peers", "ss_peer_wait", "ss_peer_error", "ss_rollout_random_packed", "ss_debug_set_id_mask",
     "ss_camera_default", "ss_body_poses", "ss_render", "ss_reset_masked", "ss_get_state_envs", "ss_set_state_envs",
     "ss_kinematics", "ss_step_forces", "ss_eom", "ss_push", "ss_lookahead",
+    "ss_lookahead_states", "ss_get_obs_states",
 ]
 NUM_BODIES = 22           # torso + 21 links: ss_body_poses rows per env
 KIN_SUMMARY, KIN_CORNER = 12, 8   # SS_KIN_SUMMARY, SS_KIN_CORNER: words of a summary row, sole corners per env (ss_kinematics)
@@ -105,6 +106,8 @@ def load():
     lib.ss_eom.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.ss_push.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
     lib.ss_lookahead.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.ss_lookahead_states.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.ss_get_obs_states.argtypes = [vp, i32, vp, vp, vp]
     if lib.ss_version() != ABI_VERSION:
         # the argument lists and struct sizes changed between versions (2: steps_per_launch in ss_rollout_random; 3: ss_info has 6
         # words, the packed state 186): a stale library would be called with the wrong layout and no error

@@ -29,7 +29,8 @@ SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"
 # against 63.2 us per call at 4096 envs, 432.7 against 434.9 at 32768
 # ss_lookahead.hip (the look-ahead: the plain step kernel's substeps, H control steps per launch) keeps it: 256 VGPRs + 254 AGPRs and no
 # scratch with it, 256 + 256 and 180 B per lane without, and 1074 against 1112 us per call of 16 steps at 4096 rows, 1138 against 1188
-# at 32768
+# at 32768.  Its second instantiation, the look-ahead from caller-supplied state rows, has the same figures, and the
+# observation of state rows (one lane per row) takes 156 VGPRs and no scratch.
 NO_MAX_ILP = {"ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"}
 HEADERS = ["ss_math.hpp", "ss_pair.hpp", "ss_dynamics.hpp", "ss_kernels.hpp", "ss_model_tables.hpp", "ss_render.hpp", "ss_visual_tables.hpp", "ss_kinematics.hpp", "ss_forces.hpp", "ss_eom.hpp", "ss_push.hpp", "ss_lookahead.hpp",
            os.path.join("..", "..", "include", "steppingstone.h")]

@@ -34,6 +34,9 @@ hipError_t launch_push(const Params& P, int kind, const int32_t* env_ids, int m,
 // compiled in ss_lookahead.hip (the look-ahead, docs/PHYSICS.md)
 hipError_t launch_lookahead(const Params& P, int kind, const int32_t* env_ids, int m, int horizon, const float* act, float* obs, float* rew,
                             uint8_t* done, float* final_state, float* work, hipStream_t st);
+hipError_t launch_lookahead_states(const Params& P, int kind, const int32_t* env_ids, int m, const float* states, int horizon,
+                                   const float* act, float* obs, float* rew, uint8_t* done, float* final_state, float* work, hipStream_t st);
+hipError_t launch_obs_states(int kind, int m, const float* states, float* obs, hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -858,6 +861,36 @@ int ss_lookahead(ss_env* env, const int32_t* env_ids, int32_t m, int32_t horizon
   if (!act || !rew || !done || !work) return fail(SS_ERR_INVALID, "ss_lookahead: act, rew, done and work are required when m > 0");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_lookahead(env->P, env->kind, env_ids, m, horizon, act, obs, rew, done, final_state, work, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_lookahead_states(ss_env* env, const int32_t* env_ids, int32_t m, const float* states, int32_t horizon, const float* act, float* obs,
+                        float* rew, uint8_t* done, float* final_state, float* work, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_lookahead_states: m must be >= 0");
+  if (horizon < 1 || horizon > SS_LOOK_MAX_STEPS)
+    return fail(SS_ERR_INVALID, "ss_lookahead_states: horizon must be in [1, SS_LOOK_MAX_STEPS]");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_lookahead_states: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (((uintptr_t)obs | (uintptr_t)rew | (uintptr_t)final_state | (uintptr_t)work) & 15)
+    return fail(SS_ERR_INVALID, "ss_lookahead_states: obs, rew, final_state and work must be 16-byte aligned");
+  if ((uintptr_t)states & 3) return fail(SS_ERR_INVALID, "ss_lookahead_states: states must be 4-byte aligned");
+  if (!states || !act || !rew || !done || !work)
+    return fail(SS_ERR_INVALID, "ss_lookahead_states: states, act, rew, done and work are required when m > 0");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_lookahead_states(env->P, env->kind, env_ids, m, states, horizon, act, obs, rew, done, final_state, work,
+                                     (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_get_obs_states(ss_env* env, int32_t m, const float* states, float* obs, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_get_obs_states: m must be >= 0");
+  if (m == 0) return SS_OK;
+  if (!states || !obs) return fail(SS_ERR_INVALID, "ss_get_obs_states: states and obs are required when m > 0");
+  if (((uintptr_t)states | (uintptr_t)obs) & 3) return fail(SS_ERR_INVALID, "ss_get_obs_states: states and obs must be 4-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_obs_states(env->kind, m, states, obs, (hipStream_t)stream));
   return SS_OK;
 }
 

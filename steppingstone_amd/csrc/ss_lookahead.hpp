@@ -14,6 +14,12 @@
 //
 // Every function is SSD (host and device): tests/host/lookahead_host.cpp runs the same code on the CPU, the 64 lanes as threads.  The
 // kernel and its launcher are in ss_lookahead.hip.
+//
+// Branches from caller-supplied states (ss_lookahead_states; PHYSICS.md 13 "Branches from caller-supplied states"): look_row<Model, true>
+// is the same function with another prologue -- the lane's half of the dynamic state, the stones and headings and the work row come from
+// row k of a packed [m,186] array (the ss_get_state layout) through unpack_env's conversions, where look_row<Model, false> reads env
+// env_ids[k]'s arrays.  The env still gives the global id (the Philox key), its row of a per-env probability grid and the knobs.  The
+// H-step loop and the epilogue are one text for both.  obs_from_row is the observation of such a row (ss_get_obs_states).
 #pragma once
 #include "ss_forces.hpp"
 
@@ -82,6 +88,99 @@ SSD void init_work(const Params& P, int e, int side, float* W) {
   }
 }
 
+// ---- a packed state row (the ss_get_state layout) as the source ----
+// The integer words of a row, as unpack_env reads them: (int) / (uint32_t) of the float.  Written out so that every float has a defined
+// result on the host as well: what v_cvt_i32_f32 / v_cvt_u32_f32 give (saturation; NaN: 0).
+SSD int row_int(float x) {
+  return x != x ? 0 : (x >= 2147483648.f ? 2147483647 : (x < -2147483648.f ? -2147483647 - 1 : (int)x));
+}
+SSD uint32_t row_u32(float x) { return !(x > 0.f) ? 0u : (x >= 4294967296.f ? 0xFFFFFFFFu : (uint32_t)x); }
+SSD uint32_t row_rng(const float* S) { return row_u32(S[62]) | (row_u32(S[63]) << 16); }
+
+// cache_from_terrain on the row's own terrain words (S[65 + 6 k ..]): the active stones n-1, n, n+1 of n = word 59 and the cos / sin of
+// their headings.  n is clamped into [0, 19] first, so that no row, whatever it holds, reads outside its 120 terrain words; for every state
+// ss_step accepts (1 <= n <= 19) the three indices are cache_from_terrain's.
+SSD void cache_from_row(const float* S, Cache& c, float (&hd)[3][2]) {
+  const int n_raw = row_int(S[59]);
+  const int n = n_raw < 0 ? 0 : (n_raw > kNumStones - 1 ? kNumStones - 1 : n_raw);
+  const int idx[3] = {n - 1 < 0 ? 0 : n - 1, n, n + 1 > kNumStones - 1 ? kNumStones - 1 : n + 1};
+#pragma unroll
+  for (int sl = 0; sl < 3; ++sl) {
+    const float* T = S + 65 + idx[sl] * 6;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c.p[sl][i] = T[i];
+    const float phi = T[3], xt = T[4], yt = T[5];
+    c.tilt[sl][0] = xt; c.tilt[sl][1] = yt;
+    stone_normal(phi, xt, yt, c.nrm[sl]);
+    sincosf(phi, &hd[sl][1], &hd[sl][0]);
+  }
+}
+
+// load_in from a row: the stones and headings and the lane's half of the dynamic state into the lane's LDS columns (words 0..54 of a row
+// are fstate's F_POS .. F_QD).  c: the active stones, for init_work_row.
+SSD void load_in_row(const float* S, int side, float m, const Lds& L, Cache& c) {
+  float hd[3][2];
+  cache_from_row(S, c, hd);
+  put_stones(L, m, c, hd);
+  float gin[13], qin[NH], qdin[NH];
+#pragma unroll
+  for (int i = 0; i < 13; ++i) gin[i] = S[F_POS + i];
+  static_for<0, NH>([&](auto Kc) {
+    constexpr int k = decltype(Kc)::value, jr = kHalf[k];
+    constexpr int jl = left_twin(jr);
+    const int gj = side ? jl : jr;
+    qin[k] = S[F_Q + gj];
+    qdin[k] = S[F_QD + gj];
+  });
+  put_base(L, m, gin, gin + 3, gin + 7, gin + 10);
+  put_joints(L, m, qin, qdin);
+}
+
+// init_work from a row: all 20 terrain rows as stored (unpack_env sets prov = 20), the active stones as load_in_row made them, the
+// env-level scalars through unpack_env's conversions
+SSD void init_work_row(const float* S, const Cache& c, int side, float* W) {
+#pragma unroll 1
+  for (int i = side * 60; i < side * 60 + 60; ++i) W[W_TERR + i] = S[65 + i];
+  if (side == 0) {
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { W[W_STONE + sl * 8 + i] = c.p[sl][i]; W[W_STONE + sl * 8 + 3 + i] = c.nrm[sl][i]; }
+      W[W_STONE + sl * 8 + 6] = c.tilt[sl][0];
+      W[W_STONE + sl * 8 + 7] = c.tilt[sl][1];
+    }
+    W[W_POT] = S[F_POT];
+    W[W_ZINIT] = S[F_ZINIT];
+    W[W_EPRET] = S[F_EPRET];
+    W[W_EPLO] = S[185];
+    W[W_NNDR] = S[F_NNDR];
+    W[W_N] = i2f(row_int(S[59]));
+    W[W_COUNT] = i2f(row_int(S[60]));
+    W[W_ELAPSED] = i2f(row_int(S[61]));
+    W[W_RNG] = i2f((int)row_rng(S));
+    W[W_FLAGS] = i2f(row_int(S[64]));
+  }
+}
+
+// The observation of a state row (ss_get_obs_states): write_obs over the row's dynamic state and active stones -- what obs_kernel writes
+// for an env that unpack_env has put the row into.  It depends on no id and no knob.
+template <class Model>
+SSD void obs_from_row(const float* S, float* o) {
+  Dyn s;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) s.pos[i] = S[F_POS + i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s.quat[i] = S[F_QUAT + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { s.v0.w[i] = S[F_VEL + i]; s.v0.v[i] = S[F_VEL + 3 + i]; }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) { s.q[j] = S[F_Q + j]; s.qd[j] = S[F_QD + j]; }
+  Cache c;
+  float hd[3][2];
+  cache_from_row(S, c, hd);
+  write_obs<Model>(s, S[F_ZINIT], row_int(S[64]), c, o);
+}
+
 // The wavefront copies the staged observation rows of step s (LDS [32][60], rows back to back) to obs[row0 + r, s, :]: every row is 15
 // contiguous float4; `okmask` bit i: the i-th float4 of this lane belongs to a row that may be written.
 SSD void copy_obs(float* obs, int row0, int H, int s, int lane, uint32_t okmask, const float* lds) {
@@ -100,9 +199,11 @@ SSD void copy_obs(float* obs, int row0, int H, int s, int lane, uint32_t okmask,
 // One branch: lane `lane_global` = 2 * row + side.  A row >= m or an env id outside [0, N) runs the whole body on a valid env (the
 // lane-pair exchanges need both lanes, the wavefront runs in lockstep) and stores nothing outside `work`; a row >= m stores nothing at all.
 // A finished branch keeps running too, with every store gated to the frozen values.
-template <class Model>
+// ROWS: the branch starts from states[row, :] instead of env e's state (a row >= m or a bad id runs on the row the lane pair was clamped
+// to, which is inside `states` either way); e stays the env whose id, probability grid and knobs the draws use.
+template <class Model, bool ROWS = false>
 SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const float* act, const Out& out, int lane_global, int lane,
-                  float* lds) {
+                  float* lds, const float* states = nullptr) {
   const int row_raw = lane_global >> 1, side = lane_global & 1;
   int row = row_raw < m ? row_raw : m - 1;                  // m >= 1
   const int e_raw = env_ids ? env_ids[row] : row;
@@ -113,8 +214,15 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
   const int row0 = (lane_global - lane) >> 1;                // first row of this wavefront
   const Lds L{lds, lane};
   float ain[NH];
-  load_in<false>(P, e, nullptr, side, m_, L, ain);            // (every step loads its own actions)
-  if (own) init_work(P, e, side, out.work + (size_t)row * SS_LOOK_WORK);
+  if constexpr (ROWS) {
+    const float* S = states + (size_t)row * SS_STATE_DIM;
+    Cache c0;
+    load_in_row(S, side, m_, L, c0);
+    if (own) init_work_row(S, c0, side, out.work + (size_t)row * SS_LOOK_WORK);
+  } else {
+    load_in<false>(P, e, nullptr, side, m_, L, ain);          // (every step loads its own actions)
+    if (own) init_work(P, e, side, out.work + (size_t)row * SS_LOOK_WORK);
+  }
   {
     uint32_t okmask = 0;
 #pragma unroll

@@ -202,6 +202,17 @@ class HipBackend:
         _lib.check(self.lib.ss_lookahead(self.h, opt(env_ids), int(m), int(horizon), _ptr(act), opt(obs), _ptr(rew), _ptr(done),
                                          opt(final_state), _ptr(work), _stream(self.device)))
 
+    def lookahead_states(self, env_ids, m, states, horizon, act, obs, rew, done, final_state, work):
+        """lookahead() with row k starting from states[k] ([m,186] float32 device tensor) instead of env env_ids[k]'s current state
+        (docs/PHYSICS.md 13, "Branches from caller-supplied states")."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_lookahead_states(self.h, opt(env_ids), int(m), _ptr(states), int(horizon), _ptr(act), opt(obs), _ptr(rew),
+                                                _ptr(done), opt(final_state), _ptr(work), _stream(self.device)))
+
+    def get_obs_states(self, m, states, obs):
+        """states [m,186] -> obs [m,60]: float32 device tensors; the observation of each state row (docs/PHYSICS.md 13)."""
+        _lib.check(self.lib.ss_get_obs_states(self.h, int(m), _ptr(states), _ptr(obs), _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
@@ -658,7 +669,32 @@ class SteppingStoneVecEnv:
             self.backend.push(ids, m, bod, pt, w, out, bool(apply))
         return out.cpu().numpy() if self.return_numpy else out
 
-    def lookahead(self, actions, env_ids=None, obs=True, final_state=False):
+    def _state_rows(self, states, what):
+        """states as a contiguous float32 tensor on the env's device; anything that is no float32 tensor / array is refused"""
+        if not (torch.is_tensor(states) or isinstance(states, np.ndarray)):
+            raise ValueError("%s: states must be a float32 tensor or array, got %s" % (what, type(states).__name__))
+        if states.dtype not in (torch.float32, np.float32):
+            raise ValueError("%s: states must be float32, got %s" % (what, states.dtype))
+        if states.ndim < 1 or states.shape[-1] != STATE_DIM:
+            raise ValueError("%s: a state row has %d words (get_state()), got shape %s" % (what, STATE_DIM, tuple(states.shape)))
+        return torch.as_tensor(states).to(self.device).contiguous()
+
+    def observe(self, states):
+        """The observation of each packed state row, on the GPU (docs/PHYSICS.md 13): states [m,186] (get_state()'s layout, float32
+        tensor or array) -> [m,60], row k what get_obs() gives after set_state(states[k]).  No env is read or written: this is the
+        observation at the root of a lookahead(states=...) branch, or of a logged state."""
+        if not hasattr(self.backend, "get_obs_states"):
+            raise NotImplementedError("this backend has no observation of state rows")
+        st = self._state_rows(states, "observe")
+        if st.dim() != 2:
+            raise ValueError("observe: states must have shape (m, %d), got %s" % (STATE_DIM, tuple(st.shape)))
+        m = int(st.shape[0])
+        out = torch.zeros((m, OBS_DIM), dtype=torch.float32, device=self.device)
+        if m:
+            self.backend.get_obs_states(m, st, out)
+        return out.cpu().numpy() if self.return_numpy else out
+
+    def lookahead(self, actions, env_ids=None, obs=True, final_state=False, states=None):
         """Dry run of H control steps per action sequence, on the GPU, from the envs' current state, which stays as it is: no state
         word, no terrain row, no RNG counter changes (docs/PHYSICS.md 13).  actions: [m,H,21], row k a BRANCH of env env_ids[k] (ids in
         [0, N), repeats welcome: B branches of an env are B rows with its id; [N,H,21] without env_ids), or [N,B,H,21] without env_ids:
@@ -666,9 +702,16 @@ class SteppingStoneVecEnv:
         sees the stones, target advances and time limit the env would see under those actions and never resets: after its first done
         step its rewards are 0, its done flags True and its observation repeats.  Returns a dict of tensors on the env's device (numpy
         arrays in numpy mode): rew [m,H], done [m,H] bool, ret [m] (the sum of the branch's rewards), obs [m,H,60] if asked for,
-        final_state [m,186] if asked for (the get_state() row the branch ends in: set_state_envs commits it)."""
+        final_state [m,186] if asked for (the get_state() row the branch ends in: set_state_envs commits it).
+        states: [m,186] float32 (get_state()'s layout; [N,B,186] with [N,B,H,21] actions): branch k starts from states[k] instead of
+        env env_ids[k]'s current state -- the final_state of an earlier call (a deeper level of a tree search), get_state() with a
+        push(apply=False) added, a perturbed or a logged state.  The env still gives its id (the stream its stones are drawn from), its
+        probability grid and the curriculum; observe(states) is the observation such a branch starts from."""
+        if states is not None and not hasattr(self.backend, "lookahead_states"):
+            raise NotImplementedError("this backend has no look-ahead from caller-supplied states")
         if not hasattr(self.backend, "lookahead"):
             raise NotImplementedError("this backend has no look-ahead")
+        st = None if states is None else self._state_rows(states, "lookahead")
         act = torch.as_tensor(actions, dtype=torch.float32).to(self.device).contiguous()
         lead = None
         if act.dim() == 4:
@@ -693,6 +736,11 @@ class SteppingStoneVecEnv:
         horizon = int(act.shape[1])
         if not 1 <= horizon <= _lib.LOOK_MAX_STEPS:
             raise ValueError("lookahead: the horizon must lie in [1, %d], got %d" % (_lib.LOOK_MAX_STEPS, horizon))
+        if st is not None:
+            want = lead + (STATE_DIM,) if lead is not None else (m, STATE_DIM)
+            if tuple(st.shape) != want:
+                raise ValueError("lookahead: these actions need states of shape %s, got %s" % (want, tuple(st.shape)))
+            st = st.reshape(m, STATE_DIM)
         ids = None if host_ids is None else torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
         new = lambda *shape: torch.zeros((m,) + shape, dtype=torch.float32, device=self.device)
         rew = new(horizon)
@@ -701,7 +749,10 @@ class SteppingStoneVecEnv:
         fs = new(STATE_DIM) if final_state else None
         if m:
             work = torch.empty((m, _lib.LOOK_WORK), dtype=torch.float32, device=self.device)
-            self.backend.lookahead(ids, m, horizon, act, ob, rew, done, fs, work)
+            if st is None:
+                self.backend.lookahead(ids, m, horizon, act, ob, rew, done, fs, work)
+            else:
+                self.backend.lookahead_states(ids, m, st, horizon, act, ob, rew, done, fs, work)
         out = {"rew": rew, "done": done.bool(), "ret": rew.sum(1)}
         if obs:
             out["obs"] = ob
@@ -941,12 +992,20 @@ class SteppingStoneEnv:
         out = self.vec.step_forces(np.asarray(action, np.float32).reshape(1, ACT_DIM))
         return {k: v[0] for k, v in out.items()}
 
-    def lookahead(self, actions, obs=True, final_state=False):
+    def lookahead(self, actions, obs=True, final_state=False, states=None):
         """Dry run of B action sequences from the current state (SteppingStoneVecEnv.lookahead): actions [B,H,21] (or [H,21]: one
-        branch) -> the dict with B rows."""
+        branch) -> the dict with B rows.  states: [B,186] (or [186] with one branch): branch b starts from states[b] instead."""
         a = np.asarray(actions, np.float32)
         a = a.reshape((-1,) + a.shape[-2:])
-        return self.vec.lookahead(a, env_ids=np.zeros(a.shape[0], np.int64), obs=obs, final_state=final_state)
+        if states is not None:
+            states = self.vec._state_rows(states, "lookahead")
+            states = states.reshape(1, STATE_DIM) if states.dim() == 1 else states
+        return self.vec.lookahead(a, env_ids=np.zeros(a.shape[0], np.int64), obs=obs, final_state=final_state, states=states)
+
+    def observe(self, states):
+        """The observation of packed state rows (SteppingStoneVecEnv.observe): states [m,186] -> [m,60]; one row [186] -> [60]."""
+        st = self.vec._state_rows(states, "observe")
+        return self.vec.observe(st.reshape(1, STATE_DIM))[0] if st.dim() == 1 else self.vec.observe(st)
 
     def equation_of_motion(self, mass=True, forces=True, jacobians=True):
         """The terms of the equation of motion at the current state (SteppingStoneVecEnv.equation_of_motion): the dict without the env axis."""

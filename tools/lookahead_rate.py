@@ -3,7 +3,8 @@
 state, beside the only route there was before it -- H launches of ss_step on as many envs, which gives one branch per env and overwrites
 the envs -- in the same process, with device events: Walker3D, curriculum 5, auto-reset off, after 30 random control steps (the method of
 tools/push_rate.py).  One branch per env, bounded random actions (most branches survive the horizon; a finished one keeps its lanes busy
-until its wavefront has nothing left).
+until its wavefront has nothing left).  The il_* figures are three series interleaved in one loop: ss_lookahead, ss_lookahead_states on the
+same rows handed in as `states`, and the set_state route that call replaces (save the envs, put the rows in, look ahead, put the envs back).
 
     python tools/lookahead_rate.py [--envs 4096,32768] [--horizon 16] [--reps 20]
     STEPPINGSTONE_LIB=var/libss_NAME.so python tools/lookahead_rate.py   (another build of the same sources: A/B in a process of its own)
@@ -53,9 +54,48 @@ def measure(kind, n, horizon, reps):
     res["lookahead_no_obs_us"] = timed(lambda: be.lookahead(None, n, horizon, act, None, rew, done, None, work), reps)
     res["steps_us"] = timed_from(env, start, real_steps, reps)
     res["lookahead_all_again_us"] = timed(lambda: be.lookahead(None, n, horizon, act, obs, rew, done, fs, work), reps)
+    # From caller-supplied states (ss_lookahead_states): the rows the env holds, handed in as `states`, so that every series below does
+    # the same work per row.  Three series interleaved call by call, each with its own events: ss_lookahead, ss_lookahead_states, and
+    # the route the latter replaces -- save the envs, put the rows in, look ahead, put the envs back.
+    ids = torch.arange(n, dtype=torch.int32, device="cuda:0")
+    saved = torch.empty_like(start)
+    env.set_state(start)
+
+    def route():
+        be.get_state_envs(ids, saved)
+        be.set_state_envs(ids, start)
+        be.lookahead(ids, n, horizon, act, obs, rew, done, fs, work)
+        be.set_state_envs(ids, saved)
+
+    series = interleaved(dict(
+        il_lookahead_us=lambda: be.lookahead(ids, n, horizon, act, obs, rew, done, fs, work),
+        il_from_states_us=lambda: be.lookahead_states(ids, n, start, horizon, act, obs, rew, done, fs, work),
+        il_set_state_route_us=route), reps)
+    res.update(series)
+    o0 = new(60)
+    res["observe_us"] = timed(lambda: be.get_obs_states(n, start, o0), reps)
     res["bytes_written_per_row"] = 4 * (horizon * 61 + 186) + horizon
     env.close()
     return res
+
+
+def interleaved(fns, reps):
+    """timed() of several calls, one call of each per round, so that drift of the clocks lands on all series alike"""
+    import numpy as np
+    for _ in range(3):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[k].append(a.elapsed_time(b) * 1e3)
+    return {k: [round(float(np.median(t)), 1), round(float(min(t)), 1), round(float(max(t)), 1)] for k, t in times.items()}
 
 
 def timed_from(env, start, fn, reps):
