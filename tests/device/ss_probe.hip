@@ -5,7 +5,9 @@
 // and one whole substep<Model, 0> on the lane pair of a robot for tests/test_substep.py / tests/substep_cases.py; and the forms the
 // step kernels use in place of older ones, each beside its reference, for the tests that require the two sides to agree BITWISE: the
 // half-broadcast packed multiply(-add) of ss_pair.hpp (tests/test_pair_broadcast.py), the joint-limit and joint-torque forms of
-// ss_dynamics.hpp (tests/test_limit_forms.py) and joint_tau's {leg, arm} pair overload (tests/test_pair_response.py).
+// ss_dynamics.hpp (tests/test_limit_forms.py) and joint_tau's {leg, arm} pair overload (tests/test_pair_response.py); and the env logic
+// of a control step behind its substeps (ss_kernels.hpp: step_logic on the lane pair, step_score and ep_return_add by value) for
+// tests/test_step_logic.py / tests/np_step_logic.py.
 // TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
 //
 // The same source is compiled two ways:
@@ -13,8 +15,8 @@
 //     takes DEVICE pointers and a stream, launches whole wavefronts of 64 (the lane exchange needs every lane active) and guards
 //     only its stores by n;
 //   * for the CPU by tests/probe_lib.py (-DSS_PROBE_HOST, the host recipe of tests/native_build.py); ssp_run loops over the cases with host pointers.
-//     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED, and every other op sees the identity -- but `substep`,
-//     whose two lanes run as two threads that meet at every exchange.
+//     The lane exchange has no meaning there: that op answers SSP_UNSUPPORTED, and every other op sees the identity -- but `substep`
+//     and `step_logic`, whose two lanes run as two threads that meet at every exchange.
 //
 //   int ssp_run(int op, int kind, int n, const float* in, float* out, void* stream)
 //     in [n][IN_W(op)], out [n][OUT_W(op)], row-major; kind 0 = ModelWalker3D, 1 = ModelMike.  Joint / body / pair numbers are
@@ -22,7 +24,7 @@
 //     (Philox, xchg_u32, xchg_i) travel as raw bits.  n == 0 reads and writes nothing and returns IN_W * 1000 + OUT_W, so that the
 //     caller sizes its buffers from the library itself.  Returns 0, or a negative SSP_* / the HIP error of the launch.
 //     An op given a joint number it is not instantiated for (see the lists below) leaves zeros.
-//   The ops from fk_detect to substep work on a lane-private Lds view as the step kernels do: on the device one __shared__ block of
+//   The ops from fk_detect to substep, and step_logic, work on a lane-private Lds view as the step kernels do: on the device one __shared__ block of
 //   kLdsSlots * kWave float4 per wavefront and Lds{base, lane}; on the host one such block per case (filled with NaN first) and lane 0.
 #include <hip/hip_runtime.h>
 
@@ -37,20 +39,31 @@
 #include <atomic>
 #include <thread>
 // The lane exchange on the host.  Every op but `substep` runs one lane per case on the calling thread, which has no partner: the
-// exchange is the identity (contact_ops forms C with the lane as its own partner; the exchange op itself is refused).  `substep` runs
-// the two lanes of a robot as two threads that meet at every exchange, as tests/host/host_harness.cpp's lanes do.
+// exchange is the identity (contact_ops forms C with the lane as its own partner; the exchange op itself is refused).  `substep` and
+// `step_logic` run the two lanes of a robot as two threads that meet at every exchange, as tests/host/host_harness.cpp's lanes do.
 namespace {
+// A lane that leaves its case while its partner waits in an exchange did not take part in it: step_logic forms `finite` as
+// finite_bits(own) && (xchg_i(...) != 0), so a lane whose own sum is not finite skips that exchange (the last one of the function).  On
+// the device the partner's DPP move then reads a disabled lane, which gives 0 (bound_ctrl), "not finite"; here the waiting lane gets the
+// same 0 once the partner is gone.
 struct PairSync {
-  std::atomic<int> arrived{0}, generation{0};
+  std::atomic<int> arrived{0}, generation{0}, gone{0};
   float slot[2];
-  void wait() {
+  bool wait() {       // false: the partner has left
     const int g = generation.load(std::memory_order_acquire);
     if (arrived.fetch_add(1, std::memory_order_acq_rel) == 1) {
       arrived.store(0, std::memory_order_relaxed);
       generation.store(g + 1, std::memory_order_release);
     } else {
-      while (generation.load(std::memory_order_acquire) == g) std::this_thread::yield();
+      while (generation.load(std::memory_order_acquire) == g) {
+        if (gone.load(std::memory_order_acquire) != 0) {
+          arrived.fetch_sub(1, std::memory_order_acq_rel);
+          return false;
+        }
+        std::this_thread::yield();
+      }
     }
+    return true;
   }
 };
 thread_local PairSync* t_sync = nullptr;      // null: no partner
@@ -60,7 +73,7 @@ float ss_host_xchg(float x) {
   PairSync* s = t_sync;
   if (!s) return x;
   s->slot[t_side] = x;
-  s->wait();
+  if (!s->wait()) return __builtin_bit_cast(float, 0u);
   const float r = s->slot[1 - t_side];
   s->wait();
   return r;
@@ -134,11 +147,27 @@ enum {
   OP_TAU_PAIR,         // [power, act (leg halves), act (arm halves), (q, qd) x joints 0..20]
                        //                                          -> per pair (3,13) (4,14) (5,15) (6,16) 8: tau leg, tau arm, Dadd leg, Dadd arm of
                        //                                             joint_tau's pair overload, then of joint_tau per joint
+  // ---- the env logic of a control step behind its substeps (PHYSICS.md 4.3-4.10).  Words that are integers to the kernels travel as raw
+  // bits, in and out.
+  OP_STEP_SCORE,       // [pos 3, quat 4, centres of the stones n-1, n, n+1 (9), target_old 3, sole 3 x right, left, pot_prev, advanced, n,
+                       //  elapsed, finite, step_bonus, e_sum, a2, at_limit]
+                       //                                          -> StepScore: pot_prev, d, bad, r, roll, pitch, cyaw, syaw
+  OP_EP_RETURN,        // [ep_ret, ep_lo, r x kEpR]                 -> (ep_ret, ep_lo) after each ep_return_add
+  // One case is one ROBOT = two lanes, as for substep; the row is the robot's, in the true world, but the foot reports, each in its lane's.
+  OP_STEP_LOGIC,       // [pos 3, quat 4, w 3, v 3, q 21, qd 21, act 21 (clipped, policy coordinates), FootReport (contact, on_target, sole 3)
+                       //  x right, left lane, cache (p 9, nrm 9, tilt 6), headings (cos, sin) x 3, pot_prev, nn_dr, ep_ret, ep_lo, n, count,
+                       //  elapsed, ctr, stub stone (p 3, nrm 3, tilt 2, heading 2, dr)]
+                       //                                          -> per lane: StepEnd (pos 3, quat 4, w 3, v 3, flags, advanced, hd 6, d, bad,
+                       //                                             r, roll, pitch, cyaw, syaw), pot_prev, nn_dr, ep_ret, ep_lo, n, count,
+                       //                                             elapsed, ctr, cache 24, the heading items of LDS 6, the draw's record:
+                       //                                             calls, k, ctr, store (of the last call)
   OP_COUNT
 };
 enum { SSP_BAD_OP = -1, SSP_UNSUPPORTED = -2, SSP_BAD_KIND = -3 };
 
 constexpr int kAbi = 21, kRec = 10;
+constexpr int kEpR = 100;                        // rewards per ep_return row: the test chains rows through the pair to longer episodes
+constexpr int kLogicIn = 13 + 3 * NJ + 10 + 24 + 6 + 8 + 11, kLogicOut = 28 + 8 + 24 + 6 + 4;
 __host__ __device__ constexpr int in_w(int op) {
   switch (op) {
     case OP_ROT: return 6;
@@ -177,11 +206,14 @@ __host__ __device__ constexpr int in_w(int op) {
     case OP_PK_HALF: return 6;
     case OP_LIMIT_FORMS: return 2 + 2 * NJ;
     case OP_TAU_PAIR: return 3 + 2 * NJ;
+    case OP_STEP_SCORE: return 3 + 4 + 9 + 3 + 6 + 1 + 8;
+    case OP_EP_RETURN: return 2 + kEpR;
+    case OP_STEP_LOGIC: return kLogicIn;
     default: return 0;
   }
 }
-__host__ __device__ constexpr bool needs_lds(int op) { return op >= OP_FK_DETECT && op <= OP_SUBSTEP; }
-__host__ __device__ constexpr int lanes_per_case(int op) { return op == OP_SUBSTEP ? 2 : 1; }      // out_w is per case: lanes x words
+__host__ __device__ constexpr bool needs_lds(int op) { return (op >= OP_FK_DETECT && op <= OP_SUBSTEP) || op == OP_STEP_LOGIC; }
+__host__ __device__ constexpr int lanes_per_case(int op) { return (op == OP_SUBSTEP || op == OP_STEP_LOGIC) ? 2 : 1; }      // out_w is per case: lanes x words
 constexpr int kSubOut = 2 * NH + 13 + 13 + 5;
 __host__ __device__ constexpr int out_w(int op) {
   switch (op) {
@@ -222,6 +254,9 @@ __host__ __device__ constexpr int out_w(int op) {
     case OP_PK_HALF: return 32;
     case OP_LIMIT_FORMS: return 10 * NJ;
     case OP_TAU_PAIR: return 32;
+    case OP_STEP_SCORE: return 8;
+    case OP_EP_RETURN: return 2 * kEpR;
+    case OP_STEP_LOGIC: return 2 * kLogicOut;
     default: return 0;
   }
 }
@@ -878,11 +913,101 @@ SSD void run_case(const float* p, float* o, const Lds& L) {
     run_limit<Model>(p, o);
   } else if constexpr (OP == OP_TAU_PAIR) {
     run_tau<Model>(p, o);
+  } else if constexpr (OP == OP_STEP_SCORE) {
+    const float pos[3] = {p[0], p[1], p[2]}, quat[4] = {p[3], p[4], p[5], p[6]};
+    Cache c = {};
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) c.p[sl][i] = p[7 + 3 * sl + i];
+    const float target_old[3] = {p[16], p[17], p[18]};
+    const float sole[2][3] = {{p[19], p[20], p[21]}, {p[22], p[23], p[24]}};
+    const StepScore sc = step_score(pos, quat, c, target_old, sole, p[25], (int)bits(p[26]), (int)bits(p[27]), (int)bits(p[28]),
+                                    bits(p[29]) != 0u, p[30], p[31], p[32], (int)bits(p[33]));
+    o[0] = sc.pot_prev; o[1] = unbits(sc.d ? 1u : 0u); o[2] = unbits((uint32_t)sc.bad);
+    o[3] = sc.r; o[4] = sc.roll; o[5] = sc.pitch; o[6] = sc.cyaw; o[7] = sc.syaw;
+  } else if constexpr (OP == OP_EP_RETURN) {
+    float ep_ret = p[0], ep_lo = p[1];
+#pragma unroll
+    for (int i = 0; i < kEpR; ++i) {
+      ep_return_add(ep_ret, ep_lo, p[2 + i]);
+      o[2 * i] = ep_ret; o[2 * i + 1] = ep_lo;
+    }
+  } else if constexpr (OP == OP_STEP_LOGIC) {
+    // the lane's LDS as step_env has it behind its substeps: base, joints, actions and heading items in the lane's own world
+    const int side = L.lane & 1;
+    const float m = side ? -1.f : 1.f;
+    put_base(L, m, p, p + 3, p + 7, p + 10);
+    float qin[NH], qdin[NH], ain[NH];
+    static_for<0, NH>([&](auto Kc) {
+      constexpr int k = decltype(Kc)::value, jr = kHalf[k], jl = left_twin(jr);
+      const int gj = side ? jl : jr;
+      qin[k] = p[13 + gj];
+      qdin[k] = p[13 + NJ + gj];
+    });
+    load_actions(p + 13 + 2 * NJ, side, ain);
+    put_joints(L, m, qin, qdin);
+    put_actions(L, m, ain);
+    const float* f = p + 13 + 3 * NJ + 5 * side;
+    FootReport fr;
+    fr.contact = (int)bits(f[0]); fr.on_target = (int)bits(f[1]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) fr.sole[i] = f[2 + i];
+    const float* cp = p + 13 + 3 * NJ + 10;
+    Cache c;
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { c.p[sl][i] = cp[3 * sl + i]; c.nrm[sl][i] = cp[9 + 3 * sl + i]; }
+      c.tilt[sl][0] = cp[18 + 2 * sl]; c.tilt[sl][1] = cp[19 + 2 * sl];
+      L.q2(kLdsHead + sl) = make_float2(cp[24 + 2 * sl], m * cp[25 + 2 * sl]);      // as put_stones places a heading
+    }
+    const float* w = cp + 30;
+    float pot_prev = w[0], nn_dr = w[1], ep_ret = w[2], ep_lo = w[3];
+    int n = (int)bits(w[4]), count = (int)bits(w[5]), elapsed = (int)bits(w[6]);
+    uint32_t ctr = bits(w[7]);
+    const float* stub = w + 8;
+    const bool store = side == 0;                // the lane that writes the table, as in step_env
+    uint32_t calls = 0u, rec_k = 0u, rec_ctr = 0u, rec_store = 0u;
+    StepEnd se;
+    step_logic<Model>(L, side, m, fr, c, pot_prev, nn_dr, ep_ret, ep_lo, n, count, elapsed, ctr, store,
+                      [&](uint32_t& ct, int k, float* sp, float* nrm, float* tilt, float* h, bool st) {
+                        calls += 1u; rec_k = (uint32_t)k; rec_ctr = ct; rec_store = st ? 1u : 0u;
+                        ct += 1u;                // a draw uses one Philox block
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) { sp[i] = stub[i]; nrm[i] = stub[3 + i]; }
+                        tilt[0] = stub[6]; tilt[1] = stub[7];
+                        h[0] = stub[8]; h[1] = stub[9];
+                        return stub[10];
+                      }, se);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { o[i] = se.pos[i]; o[7 + i] = se.v0.w[i]; o[10 + i] = se.v0.v[i]; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[3 + i] = se.quat[i];
+    o[13] = unbits((uint32_t)se.flags); o[14] = unbits((uint32_t)se.advanced);
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) { o[15 + 2 * sl] = se.hd[sl][0]; o[16 + 2 * sl] = se.hd[sl][1]; }
+    o[21] = unbits(se.d ? 1u : 0u); o[22] = unbits((uint32_t)se.bad);
+    o[23] = se.r; o[24] = se.roll; o[25] = se.pitch; o[26] = se.cyaw; o[27] = se.syaw;
+    o += 28;
+    o[0] = pot_prev; o[1] = nn_dr; o[2] = ep_ret; o[3] = ep_lo;
+    o[4] = unbits((uint32_t)n); o[5] = unbits((uint32_t)count); o[6] = unbits((uint32_t)elapsed); o[7] = unbits(ctr);
+    o += 8;
+#pragma unroll
+    for (int sl = 0; sl < 3; ++sl) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { o[3 * sl + i] = c.p[sl][i]; o[9 + 3 * sl + i] = c.nrm[sl][i]; }
+      o[18 + 2 * sl] = c.tilt[sl][0]; o[19 + 2 * sl] = c.tilt[sl][1];
+      const float2 hl = L.q2(kLdsHead + sl);
+      o[24 + 2 * sl] = hl.x; o[25 + 2 * sl] = hl.y;
+    }
+    o += 30;
+    o[0] = unbits(calls); o[1] = unbits(rec_k); o[2] = unbits(rec_ctr); o[3] = unbits(rec_store);
   }
 }
 
 #if !defined(SS_PROBE_HOST)
-// one wavefront per workgroup, one case per lane (`substep`: per lane pair; a lane's share of the output row is OW words).  Lanes past
+// one wavefront per workgroup, one case per lane (`substep`, `step_logic`: per lane pair; a lane's share of the output row is OW words).  Lanes past
 // the last case redo case n - 1 (every lane stays active and reads inside the buffer; a lane keeps its side, so a pair stays a pair); only
 // lanes of a case below n store.
 template <class Model, int OP>
@@ -892,7 +1017,7 @@ __global__ __launch_bounds__(kWave) void probe_kernel(int n, const float* __rest
   const int cas = idx / LPC;
   const int src = cas < n ? cas : n - 1;
   float o[OW];
-  // `substep` reads its row where it lies: 128 words held in registers across the call would only spill
+  // a lane pair's op reads its row where it lies: 128 words held in registers across the call would only spill
   float rowbuf[LPC == 1 ? IW : 1];
   const float* row = in + (size_t)src * IW;
   if constexpr (LPC == 1) {
@@ -938,6 +1063,7 @@ int run(int op, int n, const float* in, float* out, void* stream) {
           t_side = side;
           run_case<Model, OP>(in + (size_t)e * in_w(OP), o + side * (out_w(OP) / 2), Lds{lds.data(), side});
           t_sync = nullptr;
+          sync.gone.store(1, std::memory_order_release);
         };
         std::thread partner(lane, 1);
         lane(0);

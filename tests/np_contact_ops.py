@@ -23,7 +23,7 @@ U = ns.U
 KINDS = ns.KINDS
 N_RANDOM = 2048
 # external constants: OpenCL 3.0 full profile, single precision, in ulp
-OPENCL_ULP = {"sincos": 4, "asin": 4, "atan2": 6, "sqrt": 3}
+OPENCL_ULP = {"sincos": 4, "asin": 4, "atan2": 6, "sqrt": 3, "exp": 3}
 K_SINCOS, K_ASIN, K_ATAN2, K_SQRT = (2 * OPENCL_ULP[f] for f in ("sincos", "asin", "atan2", "sqrt"))
 K_RSQRT = 2
 F32 = np.float32

@@ -8,7 +8,10 @@ the C oracle's env logic on the CPU (tests/test_oracle_env_numpy.py) and is comp
 
 Not covered (the caller skips such env-steps): a step on which the target advances (the next stone is re-drawn by the
 sampler, PHYSICS.md 6) and the reset observation of a finished episode (PHYSICS.md 7) -- both are Philox-driven and pinned
-bit-exactly elsewhere (tests/test_gpu_parity.py::test_target_advance_and_sampler_are_bit_exact)."""
+bit-exactly elsewhere (tests/test_gpu_parity.py::test_target_advance_and_sampler_are_bit_exact).  The env logic of the advance
+step itself -- the cache and heading shift, the potential re-based on the new target, the draw's call -- is held to the fp64
+reference of tests/np_step_logic.py by tests/test_step_logic.py::test_step_logic, with a stub stone in place of the draw;
+test_reference_is_np_env_on_steps_without_advance there anchors that reference on this module's control_step."""
 import numpy as np
 
 import np_contact as npc
@@ -125,6 +128,8 @@ def control_step(m, st, act):
     st[COUNT], st[ELAPSED] = count, elapsed
     return dict(state55=st[:55].copy(), obs=observation(m, st, flags, n), rew=float(rew), done=bool(done), bad=bool(timeout),
                 flags=flags, count=count, advance=advance, n=n,
+                # what the env logic was given by the last substep's detector (tests/test_step_logic.py feeds its reference with them)
+                soles=[np.array(s) for s in soles], on_target=bool(on_target),
                 # distances of the step's switching quantities from their thresholds (for callers that compare with fp32 code)
                 margins=dict(height=abs(height - 0.7), low=abs(pos[2] - zlow - 0.3), pitch=min(abs(pitch + 0.2), abs(pitch - 0.4)),
                              roll=min(abs(roll + 0.4), abs(roll - 0.4)), qn=float(np.min(np.abs(np.abs(qn) - 0.99)))))

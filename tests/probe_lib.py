@@ -1,5 +1,5 @@
-"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas, one whole substep and
-the forms that must agree bitwise with the ones they replaced, behind one C entry, one operator per call.
+"""Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas, one whole substep, the env
+logic of a control step and the forms that must agree bitwise with the ones they replaced, behind one C entry, one operator per call.
     host flavour:   compiled here for the CPU (the recipe of native_build.py) into tests/host/libss_probe_host.so, numpy pointers;
     device flavour: steppingstone_amd/lib/libss_probe.so, built for gfx950 by steppingstone_amd.build.build_probe(), torch tensors.
 TEST INFRASTRUCTURE; never imported by steppingstone_amd."""
@@ -19,7 +19,7 @@ OPS = ["rot", "rot2", "cross_r", "cross_rP", "xmotion", "xforce", "xmotionP", "x
        "abi_add_bodyP", "body_bias", "body_biasP", "imp_up", "imp_down", "imp_down_pair", "imp_up_pair", "imp_down_pair_loaded",
        "aba_acc", "aba_accP", "quat_rot", "mirror_sv", "abi_dense", "pack", "sincos", "chol", "xchg", "philox",
        "fk_detect", "jacobian_rows", "contact_ops", "sampler", "window_prob", "obs_terms", "substep",
-       "pk_half", "limit_forms", "tau_pair"]
+       "pk_half", "limit_forms", "tau_pair", "step_score", "ep_return", "step_logic"]
 OP = {name: i for i, name in enumerate(OPS)}
 UNSUPPORTED = -2
 
