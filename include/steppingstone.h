@@ -377,6 +377,50 @@ int ss_lookahead_states(ss_env* env, const int32_t* env_ids, int32_t m, const fl
  * synchronises the host, allocates nothing, can be captured into a graph.  Bad host arguments return SS_ERR_INVALID and launch nothing. */
 int ss_get_obs_states(ss_env* env, int32_t m, const float* states, float* obs, void* stream);
 
+/* Closed-loop look-ahead (docs/PHYSICS.md 14 "Branches under a policy"); added under version 4 (nothing existing moved).  The actions
+ * of a branch come from a small frozen MLP f evaluated inside the launch: with o[k,-1] the observation at the root of branch k (bit for
+ * bit ss_get_obs_states of states[k, :], or ss_get_obs of env env_ids[k] when states == NULL) and o[k,s] the observation after step s,
+ *     a[k,s] = f(o[k,s-1]) + act_offset[k,s]        (offset 0 without act_offset; f in f32)
+ * is the action of step s, which is ss_step's control step under a[k,s] (clipped there; a NaN ends the episode there).
+ *
+ * The network: `layers` fully connected layers y = activation(W x + b), widths width[0] = 60 (an observation) .. width[layers] = 21 (an
+ * action).  ss_policy_words: f32 words of the packed form of such a network, -1 for a description that is not valid.  ss_policy_pack: a
+ * device-side repack of the layers' weights (torch's nn.Linear.weight, [out, in] row-major) and biases into `packed`; ordered on
+ * `stream`, can be captured into a graph, never synchronises the host; call it again after the weights changed.  weight and bias are
+ * HOST arrays of `layers` DEVICE pointers, read during the call only; the arrays they point to are read on the stream.  The packed
+ * layout (tiled for the kernel's matrix instructions, zero padded) is OPAQUE: it may change with any release and is valid only for the
+ * library that packed it.
+ *
+ * ss_lookahead_policy: everything not said here is ss_lookahead's / ss_lookahead_states', word for word -- env_ids conventions (NULL:
+ * envs 0..m-1, needs m == N; an id outside [0, N) is skipped, nothing of it is written, `act` included), m == 0 does nothing, repeated
+ * ids, frozen rows behind a first done, the time limit, the 16-byte alignment of obs, rew, final_state and work (act and act_offset:
+ * 4-byte), SS_LOOK_WORK words of workspace per row, no host synchronisation, no allocation, capturable.  The env is only read.
+ *   states: NULL (each branch starts where its env stands) or DEVICE [m, SS_STATE_DIM] as in ss_lookahead_states.
+ *   d, packed: the description and the blob ss_policy_pack wrote for it (16-byte aligned).
+ *   act_offset: NULL or DEVICE [m, horizon, 21] f32 (exploration noise, a perturbation sequence of a sampling planner).
+ *   act: NULL or DEVICE [m, horizon, 21] f32: a[k,s], unclipped; 0.0f for every step behind the branch's first done.
+ * Given the reported actions the physics is ss_lookahead's: obs, rew, done and final_state are bit for bit what ss_lookahead /
+ * ss_lookahead_states write for the same rows under `act`.  A row's bits, actions included, depend on its id, its state, the knobs, the
+ * policy and its offsets alone: not on N, m, k, on which outputs were asked for, or on the horizon (prefix property as in ss_lookahead).
+ * NOT bitwise: f itself against another evaluation of the same network (torch, a CPU build of this library's code): the kernel sums each
+ * dot product as one f32 fma chain in index order starting from the bias, others sum in other orders; tanh and the division of softsign
+ * may differ by a few ulp between implementations.  tests/test_gpu_lookahead_policy.py holds the difference to 8 x the error of a plain
+ * f32 evaluation against fp64. */
+#define SS_POLICY_MAX_LAYERS 8
+#define SS_POLICY_MAX_WIDTH  256
+enum { SS_POLICY_IDENTITY = 0, SS_POLICY_RELU = 1, SS_POLICY_SOFTSIGN = 2, SS_POLICY_TANH = 3 };
+typedef struct {
+  int32_t layers;                                   /* 1 .. SS_POLICY_MAX_LAYERS */
+  int32_t width[SS_POLICY_MAX_LAYERS + 1];          /* width[0] == 60, width[layers] == 21, others 1 .. SS_POLICY_MAX_WIDTH */
+  int32_t activation[SS_POLICY_MAX_LAYERS];         /* one of SS_POLICY_* per layer */
+} ss_policy_desc;
+int64_t ss_policy_words(const ss_policy_desc* d);
+int ss_policy_pack(ss_env* env, const ss_policy_desc* d, const float* const* weight, const float* const* bias, float* packed,
+                   void* stream);
+int ss_lookahead_policy(ss_env* env, const int32_t* env_ids, int32_t m, const float* states, int32_t horizon, const ss_policy_desc* d,
+                        const float* packed, const float* act_offset, float* act, float* obs, float* rew, uint8_t* done,
+                        float* final_state, float* work, void* stream);
+
 /* Measurement aids (tools/hbm_traffic.py, tools/phase_profile.py); not part of the env protocol.
  * ss_debug_calib_copy: dword-per-lane copy out[i] = in[i] + 1 used to calibrate the HBM PMC counters.
  * ss_debug_phase_cycles: 16 per-phase shader-clock totals (zeros unless built with -DSS_PROFILE_PHASES). */

@@ -9,7 +9,7 @@ from ._lib import ACT_DIM, OBS_DIM, SteppingStoneError  # noqa: F401
 
 def __getattr__(name):
     # envs needs torch; keep `import steppingstone_amd` light for the build / model tooling
-    if name in ("make_env", "make_vec_envs", "SteppingStoneVecEnv", "SteppingStoneEnv", "HipBackend", "Box"):
+    if name in ("make_env", "make_vec_envs", "SteppingStoneVecEnv", "SteppingStoneEnv", "HipBackend", "Box", "pack_policy", "PackedPolicy"):
         from . import envs
         return getattr(envs, name)
     raise AttributeError(name)

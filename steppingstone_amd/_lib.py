@@ -22,7 +22,7 @@ SYMBOLS = [
     "ss_step_packed_peers", "ss_peer_wait", "ss_peer_error", "ss_rollout_random_packed", "ss_debug_set_id_mask",
     "ss_camera_default", "ss_body_poses", "ss_render", "ss_reset_masked", "ss_get_state_envs", "ss_set_state_envs",
     "ss_kinematics", "ss_step_forces", "ss_eom", "ss_push", "ss_lookahead",
-    "ss_lookahead_states", "ss_get_obs_states",
+    "ss_lookahead_states", "ss_get_obs_states", "ss_policy_words", "ss_policy_pack", "ss_lookahead_policy",
 ]
 NUM_BODIES = 22           # torso + 21 links: ss_body_poses rows per env
 KIN_SUMMARY, KIN_CORNER = 12, 8   # SS_KIN_SUMMARY, SS_KIN_CORNER: words of a summary row, sole corners per env (ss_kinematics)
@@ -30,6 +30,8 @@ FRC_SUBSTEPS, FRC_CONTACT, FRC_JOINT, FRC_STATE = 4, 8, 4, 56   # SS_FRC_*: subs
 EOM_DOF, EOM_FORCES = 27, 3        # SS_EOM_DOF, SS_EOM_FORCES: generalised coordinates (6 base + 21 joints), rows of `forces` (ss_eom)
 PUSH_WRENCH = 6                    # SS_PUSH_WRENCH: words of an impulse row, p | L (ss_push)
 LOOK_MAX_STEPS, LOOK_WORK = 1000, 160   # SS_LOOK_MAX_STEPS, SS_LOOK_WORK: longest horizon, f32 words of workspace per row (ss_lookahead)
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 8, 256   # SS_POLICY_MAX_LAYERS, SS_POLICY_MAX_WIDTH (ss_lookahead_policy)
+POLICY_IDENTITY, POLICY_RELU, POLICY_SOFTSIGN, POLICY_TANH = 0, 1, 2, 3      # SS_POLICY_*: a layer's activation
 CAM_TRACK, CAM_CHASE, CAM_FIXED = 0, 1, 2     # ss_camera.mode
 CAM_SHADOWS = 1                                # ss_camera.flags bit 0
 
@@ -38,6 +40,11 @@ class Camera(C.Structure):
     """ss_camera (include/steppingstone.h, docs/RENDER.md 1)."""
     _fields_ = [("mode", C.c_int32), ("eye", C.c_float * 3), ("target", C.c_float * 3), ("fov_y_deg", C.c_float),
                 ("far_m", C.c_float), ("flags", C.c_int32)]
+
+
+class PolicyDesc(C.Structure):
+    """ss_policy_desc (include/steppingstone.h): a small MLP, 60 -> ... -> 21."""
+    _fields_ = [("layers", C.c_int32), ("width", C.c_int32 * (POLICY_MAX_LAYERS + 1)), ("activation", C.c_int32 * POLICY_MAX_LAYERS)]
 
 
 class SteppingStoneError(RuntimeError):
@@ -108,6 +115,10 @@ def load():
     lib.ss_lookahead.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.ss_lookahead_states.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.ss_get_obs_states.argtypes = [vp, i32, vp, vp, vp]
+    lib.ss_policy_words.argtypes = [vp]
+    lib.ss_policy_words.restype = i64
+    lib.ss_policy_pack.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.ss_lookahead_policy.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if lib.ss_version() != ABI_VERSION:
         # the argument lists and struct sizes changed between versions (2: steps_per_launch in ss_rollout_random; 3: ss_info has 6
         # words, the packed state 186): a stale library would be called with the wrong layout and no error

@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libsteppingstone.so")
-SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip", "ss_forces.hip", "ss_eom.hip", "ss_push.hip", "ss_lookahead.hip"]
+SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip", "ss_forces.hip", "ss_eom.hip", "ss_push.hip", "ss_lookahead.hip", "ss_policy.hip"]
 # ss_rollout3.hip (the three-helper rollout kernel) is compiled without the max-ILP scheduling strategy: see its header.  So is
 # ss_render.hip: the render kernel is 9 % faster without it (4096 envs at 64 x 64, RGB + depth + seg, shadows: 0.889 against 0.977 ms
 # per call; DESIGN.md "Rendering").  So is ss_kinematics.hip: the strategy buys the readout no time and costs it registers -- 64 VGPRs
@@ -31,8 +31,10 @@ SOURCES = ["ss_api.hip", "ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"
 # scratch with it, 256 + 256 and 180 B per lane without, and 1074 against 1112 us per call of 16 steps at 4096 rows, 1138 against 1188
 # at 32768.  Its second instantiation, the look-ahead from caller-supplied state rows, has the same figures, and the
 # observation of state rows (one lane per row) takes 156 VGPRs and no scratch.
+# ss_policy.hip (the closed-loop look-ahead: look_row with an MLP between the control steps, four wavefronts per workgroup) keeps it, as
+# the look-ahead whose per-lane code it instantiates (DESIGN.md 5.3 has its figures).
 NO_MAX_ILP = {"ss_rollout3.hip", "ss_render.hip", "ss_kinematics.hip"}
-HEADERS = ["ss_math.hpp", "ss_pair.hpp", "ss_dynamics.hpp", "ss_kernels.hpp", "ss_model_tables.hpp", "ss_render.hpp", "ss_visual_tables.hpp", "ss_kinematics.hpp", "ss_forces.hpp", "ss_eom.hpp", "ss_push.hpp", "ss_lookahead.hpp",
+HEADERS = ["ss_math.hpp", "ss_pair.hpp", "ss_dynamics.hpp", "ss_kernels.hpp", "ss_model_tables.hpp", "ss_render.hpp", "ss_visual_tables.hpp", "ss_kinematics.hpp", "ss_forces.hpp", "ss_eom.hpp", "ss_push.hpp", "ss_lookahead.hpp", "ss_policy.hpp",
            os.path.join("..", "..", "include", "steppingstone.h")]
 # -O3 without the SLP vectorizer, signed zeros not honoured.  Measured on gfx950 / ROCm 7.2:
 #   * SLP vectorisation (packed v_pk_fma_f32 / v_pk_mul_f32) miscompiled the 1-env-per-lane kernel of v1-v3 (wrong,

@@ -37,6 +37,11 @@ hipError_t launch_lookahead(const Params& P, int kind, const int32_t* env_ids, i
 hipError_t launch_lookahead_states(const Params& P, int kind, const int32_t* env_ids, int m, const float* states, int horizon,
                                    const float* act, float* obs, float* rew, uint8_t* done, float* final_state, float* work, hipStream_t st);
 hipError_t launch_obs_states(int kind, int m, const float* states, float* obs, hipStream_t st);
+// compiled in ss_policy.hip (the closed-loop look-ahead, docs/PHYSICS.md 14), which defines ss_policy_words as well
+hipError_t launch_policy_pack(const ss_policy_desc* d, const float* const* weight, const float* const* bias, float* packed, hipStream_t st);
+hipError_t launch_lookahead_policy(const Params& P, int kind, const int32_t* env_ids, int m, const float* states, int horizon,
+                                   const ss_policy_desc* d, const float* packed, const float* offset, float* act, float* obs, float* rew,
+                                   uint8_t* done, float* final_state, float* work, hipStream_t st);
 }  // namespace ss
 
 // The kernels of the C ABI besides the step, reset and observation kernels.  Only this unit launches them: `static`, so that they
@@ -891,6 +896,41 @@ int ss_get_obs_states(ss_env* env, int32_t m, const float* states, float* obs, v
   if (((uintptr_t)states | (uintptr_t)obs) & 3) return fail(SS_ERR_INVALID, "ss_get_obs_states: states and obs must be 4-byte aligned");
   SS_HIP(hipSetDevice(env->device));
   SS_HIP(ss::launch_obs_states(env->kind, m, states, obs, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_policy_pack(ss_env* env, const ss_policy_desc* d, const float* const* weight, const float* const* bias, float* packed, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (ss_policy_words(d) < 0) return fail(SS_ERR_INVALID, "ss_policy_pack: not a valid policy description");
+  if (!weight || !bias || !packed) return fail(SS_ERR_INVALID, "ss_policy_pack: weight, bias and packed are required");
+  for (int l = 0; l < d->layers; ++l) {
+    if (!weight[l] || !bias[l]) return fail(SS_ERR_INVALID, "ss_policy_pack: a layer's weight or bias is NULL");
+    if (((uintptr_t)weight[l] | (uintptr_t)bias[l]) & 3) return fail(SS_ERR_INVALID, "ss_policy_pack: weight and bias must be 4-byte aligned");
+  }
+  if ((uintptr_t)packed & 15) return fail(SS_ERR_INVALID, "ss_policy_pack: packed must be 16-byte aligned");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_policy_pack(d, weight, bias, packed, (hipStream_t)stream));
+  return SS_OK;
+}
+
+int ss_lookahead_policy(ss_env* env, const int32_t* env_ids, int32_t m, const float* states, int32_t horizon, const ss_policy_desc* d,
+                        const float* packed, const float* act_offset, float* act, float* obs, float* rew, uint8_t* done,
+                        float* final_state, float* work, void* stream) {
+  if (!env) return fail(SS_ERR_INVALID, "null handle");
+  if (m < 0) return fail(SS_ERR_INVALID, "ss_lookahead_policy: m must be >= 0");
+  if (horizon < 1 || horizon > SS_LOOK_MAX_STEPS)
+    return fail(SS_ERR_INVALID, "ss_lookahead_policy: horizon must be in [1, SS_LOOK_MAX_STEPS]");
+  if (ss_policy_words(d) < 0) return fail(SS_ERR_INVALID, "ss_lookahead_policy: not a valid policy description");
+  if (m == 0) return SS_OK;
+  if (!env_ids && m != env->P.n) return fail(SS_ERR_INVALID, "ss_lookahead_policy: env_ids == NULL (envs 0..m-1) needs m == num_envs");
+  if (((uintptr_t)obs | (uintptr_t)rew | (uintptr_t)final_state | (uintptr_t)work | (uintptr_t)packed) & 15)
+    return fail(SS_ERR_INVALID, "ss_lookahead_policy: packed, obs, rew, final_state and work must be 16-byte aligned");
+  if (((uintptr_t)states | (uintptr_t)act_offset | (uintptr_t)act) & 3)
+    return fail(SS_ERR_INVALID, "ss_lookahead_policy: states, act_offset and act must be 4-byte aligned");
+  if (!packed || !rew || !done || !work) return fail(SS_ERR_INVALID, "ss_lookahead_policy: packed, rew, done and work are required when m > 0");
+  SS_HIP(hipSetDevice(env->device));
+  SS_HIP(ss::launch_lookahead_policy(env->P, env->kind, env_ids, m, states, horizon, d, packed, act_offset, act, obs, rew, done, final_state,
+                                     work, (hipStream_t)stream));
   return SS_OK;
 }
 

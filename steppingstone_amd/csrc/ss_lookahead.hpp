@@ -196,14 +196,23 @@ SSD void copy_obs(float* obs, int row0, int H, int s, int lane, uint32_t okmask,
   }
 }
 
+// Where a branch's actions come from, a compile-time choice of look_row.  ActGiven: row s of the caller's sequence act[k, s, :]
+// (load_actions), the look-ahead as it was.  A source with kPolicy (ss_policy.hpp) computes them between the control steps from the
+// observation rows staged in LDS region A, which look_row then stages whether or not the caller asked for obs:
+//   root_obs<Model, ROWS>(P, e, states, row, lane, lds)   the observation at the branch's root into the lane pair's staged row
+//   phase(lds, lane)                            every wavefront of the workgroup: staged rows -> the wavefront's 32 action rows
+//   emit(row, H, s, lane, valid, live)          adds the row's offset, reports the action (zeros for a finished branch)
+//   load(lane, side, ain)                       load_actions from those rows
+struct ActGiven { static constexpr bool kPolicy = false; };
+
 // One branch: lane `lane_global` = 2 * row + side.  A row >= m or an env id outside [0, N) runs the whole body on a valid env (the
 // lane-pair exchanges need both lanes, the wavefront runs in lockstep) and stores nothing outside `work`; a row >= m stores nothing at all.
 // A finished branch keeps running too, with every store gated to the frozen values.
 // ROWS: the branch starts from states[row, :] instead of env e's state (a row >= m or a bad id runs on the row the lane pair was clamped
 // to, which is inside `states` either way); e stays the env whose id, probability grid and knobs the draws use.
-template <class Model, bool ROWS = false>
+template <class Model, bool ROWS = false, class Src = ActGiven>
 SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const float* act, const Out& out, int lane_global, int lane,
-                  float* lds, const float* states = nullptr) {
+                  float* lds, const float* states = nullptr, const Src& src = Src()) {
   const int row_raw = lane_global >> 1, side = lane_global & 1;
   int row = row_raw < m ? row_raw : m - 1;                  // m >= 1
   const int e_raw = env_ids ? env_ids[row] : row;
@@ -223,6 +232,7 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
     load_in<false>(P, e, nullptr, side, m_, L, ain);          // (every step loads its own actions)
     if (own) init_work(P, e, side, out.work + (size_t)row * SS_LOOK_WORK);
   }
+  if constexpr (Src::kPolicy) src.template root_obs<Model, ROWS>(P, e, states, row, lane, lds);
   {
     uint32_t okmask = 0;
 #pragma unroll
@@ -242,9 +252,14 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
     const int fin = f2i(L.q2(kLdsNote).x);                   // finished in an earlier step: 1 + that step
     float r_out = 0.f;
     int d_out = 1;
+    if constexpr (Src::kPolicy) {
+      src.phase(lds, lane);
+      src.emit(row, H, s, lane, valid, fin == 0);
+    }
     // wavefront-uniform: nothing of this wavefront is left to compute, the frozen rows below are all that remains
     if (!SS_LOOK_ALL(fin != 0 || !valid)) {
-      load_actions(act + ((size_t)row * (size_t)H + (size_t)s) * NJ, side, ain);
+      if constexpr (Src::kPolicy) src.load(lane, side, ain);
+      else load_actions(act + ((size_t)row * (size_t)H + (size_t)s) * NJ, side, ain);
       put_actions(L, m_, ain);
       const float power = P.knobs->power;
       FootReport fr;
@@ -313,7 +328,7 @@ SSD void look_row(const Params& P, const int32_t* env_ids, int m, int H, const f
         d_out = d ? 1 : 0;
       }
       // 10. the observation row of a live branch: staged in LDS region A as emit_outputs does
-      if (out.obs) {
+      if (out.obs || Src::kPolicy) {
         SS_WAVE_SYNC();          // the staging area is region A: every lane must be through with its contact operators
         if (live) {
           float* stage = lds + (lane >> 1) * SS_OBS_DIM;

@@ -213,11 +213,130 @@ class HipBackend:
         """states [m,186] -> obs [m,60]: float32 device tensors; the observation of each state row (docs/PHYSICS.md 13)."""
         _lib.check(self.lib.ss_get_obs_states(self.h, int(m), _ptr(states), _ptr(obs), _stream(self.device)))
 
+    def policy_pack(self, desc, weights, biases, packed):
+        """desc: _lib.PolicyDesc; weights / biases: one contiguous float32 device tensor per layer ([out,in] / [out]); packed: float32
+        device tensor of ss_policy_words(desc) words (docs/PHYSICS.md 14).  Stream-ordered: a later change of the weights needs a new call."""
+        n = int(desc.layers)
+        wp = (C.c_void_p * n)(*[_ptr(w) for w in weights])
+        bp = (C.c_void_p * n)(*[_ptr(b) for b in biases])
+        _lib.check(self.lib.ss_policy_pack(self.h, C.byref(desc), wp, bp, _ptr(packed), _stream(self.device)))
+
+    def lookahead_policy(self, env_ids, m, states, horizon, desc, packed, offsets, act, obs, rew, done, final_state, work):
+        """lookahead() / lookahead_states() (states None / [m,186]) with the actions computed in the launch by the packed MLP; offsets
+        [m,H,21] or None is added to them, act [m,H,21] or None receives them (docs/PHYSICS.md 14)."""
+        opt = lambda t: _ptr(t) if t is not None else None
+        _lib.check(self.lib.ss_lookahead_policy(self.h, opt(env_ids), int(m), opt(states), int(horizon), C.byref(desc), _ptr(packed),
+                                                opt(offsets), opt(act), opt(obs), _ptr(rew), _ptr(done), opt(final_state), _ptr(work),
+                                                _stream(self.device)))
+
     def render(self, env_ids, width, height, camera, rgb, depth, seg):
         """env_ids: int32 device tensor [M]; rgb / depth / seg: device tensors or None (docs/RENDER.md)."""
         opt = lambda t: _ptr(t) if t is not None else None
         _lib.check(self.lib.ss_render(self.h, _ptr(env_ids), int(env_ids.numel()), int(width), int(height), C.byref(camera),
                                       opt(rgb), opt(depth), opt(seg), _stream(self.device)))
+
+
+POLICY_SOURCES = ("a ppo.Actor, a ppo.ActorCritic (its actor), an nn.Sequential of nn.Linear each followed by at most one of nn.ReLU / "
+                  "nn.Softsign / nn.Tanh / nn.Identity, or a list of (weight [out,in], bias [out], activation) triples with activation one "
+                  "of 'identity', 'relu', 'softsign', 'tanh'; %d -> ... -> %d, at most %d layers, at most %d wide"
+                  % (OBS_DIM, ACT_DIM, _lib.POLICY_MAX_LAYERS, _lib.POLICY_MAX_WIDTH))
+_POLICY_ACT = {"identity": _lib.POLICY_IDENTITY, "relu": _lib.POLICY_RELU, "softsign": _lib.POLICY_SOFTSIGN, "tanh": _lib.POLICY_TANH}
+
+
+def _policy_layers(source):
+    """source -> list of (weight, bias, activation code); weight / bias: tensors, parameters or arrays, read again by every refresh()"""
+    nn = torch.nn
+    from . import ppo
+    if isinstance(source, ppo.ActorCritic):
+        source = source.actor
+    if isinstance(source, ppo.Actor):
+        s = source
+        return [(s.fc1.weight, s.fc1.bias, _lib.POLICY_SOFTSIGN), (s.fc2.weight, s.fc2.bias, _lib.POLICY_SOFTSIGN),
+                (s.fc3.weight, s.fc3.bias, _lib.POLICY_SOFTSIGN), (s.fc4.weight, s.fc4.bias, _lib.POLICY_RELU),
+                (s.fc5.weight, s.fc5.bias, _lib.POLICY_RELU), (s.out.weight, s.out.bias, _lib.POLICY_TANH)]
+    kinds = {nn.ReLU: _lib.POLICY_RELU, nn.Softsign: _lib.POLICY_SOFTSIGN, nn.Tanh: _lib.POLICY_TANH, nn.Identity: _lib.POLICY_IDENTITY}
+    if isinstance(source, nn.Sequential):
+        out = []
+        for mod in source:
+            if isinstance(mod, nn.Linear):
+                if mod.bias is None:
+                    raise ValueError("pack_policy: a Linear without bias is not supported; supported: " + POLICY_SOURCES)
+                out.append([mod.weight, mod.bias, None])
+            elif type(mod) in kinds and out and out[-1][2] is None:
+                out[-1][2] = kinds[type(mod)]
+            else:
+                raise ValueError("pack_policy: %s at this place is not supported; supported: %s" % (type(mod).__name__, POLICY_SOURCES))
+        return [(w, b, _lib.POLICY_IDENTITY if a is None else a) for w, b, a in out]
+    if isinstance(source, (list, tuple)) and source and all(isinstance(t, (list, tuple)) and len(t) == 3 for t in source):
+        out = []
+        for w, b, a in source:
+            if not (isinstance(a, str) and a in _POLICY_ACT):
+                raise ValueError("pack_policy: activation %r is not supported; supported: %s" % (a, POLICY_SOURCES))
+            out.append((w, b, _POLICY_ACT[a]))
+        return out
+    raise ValueError("pack_policy: %s is not supported; supported: %s" % (type(source).__name__, POLICY_SOURCES))
+
+
+class PackedPolicy:
+    """A frozen MLP in the form the closed-loop look-ahead reads (SteppingStoneVecEnv.lookahead_policy): `desc` (_lib.PolicyDesc) and
+    `blob`, a float32 tensor on `device` whose layout is the library's own.  refresh() repacks from the same modules / arrays after their
+    values changed (a stream-ordered kernel launch: it can be captured into a graph together with the look-ahead, and a replay then
+    repacks from the parameters' current values, provided they are float32 tensors on the device already).  The repack is a call of the
+    library on an env's handle: a policy made with a torch device is packed when an env first uses it, one made with an env at once."""
+
+    def __init__(self, source, device):
+        env = device if hasattr(device, "backend") or hasattr(device, "vec") else None
+        if env is not None:
+            env = getattr(env, "vec", env)
+            device = env.device
+        self.device = torch.device(device)
+        self._layers = _policy_layers(source)
+        shapes = [(tuple(w.shape), tuple(b.shape)) for w, b, _ in self._layers]
+        if any(len(ws) != 2 or bs != (ws[0],) for ws, bs in shapes):
+            raise ValueError("pack_policy: a layer is weight [out,in] and bias [out], got %s; supported: %s" % (shapes, POLICY_SOURCES))
+        if len(shapes) > _lib.POLICY_MAX_LAYERS or any(shapes[i][0][1] != shapes[i - 1][0][0] for i in range(1, len(shapes))):
+            raise ValueError("pack_policy: the layers do not chain: %s; supported: %s" % ([ws for ws, _ in shapes], POLICY_SOURCES))
+        d = _lib.PolicyDesc()
+        d.layers = len(shapes)
+        d.width[0] = shapes[0][0][1]
+        for i, ((wo, _), _) in enumerate(shapes):
+            d.width[i + 1] = wo
+            d.activation[i] = self._layers[i][2]
+        words = int(_lib.load().ss_policy_words(C.byref(d)))
+        if words < 0:
+            raise ValueError("pack_policy: widths %s are not supported; supported: %s" % (list(d.width[:d.layers + 1]), POLICY_SOURCES))
+        self.desc = d
+        self.blob = torch.zeros(words, dtype=torch.float32, device=self.device)
+        self._backend, self._fresh, self._held = None, False, None
+        if env is not None:
+            self.bind(env.backend)
+
+    def _arrays(self):
+        """the layers' current values as contiguous float32 tensors on the device: the parameters themselves where they are that already"""
+        give = lambda t: (t.detach() if torch.is_tensor(t) else torch.as_tensor(np.array(t, dtype=np.float32))).to(self.device, torch.float32).contiguous()
+        return [give(w) for w, _, _ in self._layers], [give(b) for _, b, _ in self._layers]
+
+    def refresh(self):
+        """repack after the weights changed (now if an env has used the policy already, else at its first use)"""
+        if self._backend is None:
+            self._fresh = False
+            return self
+        ws, bs = self._arrays()
+        self._held = (ws, bs)            # the launch reads them asynchronously
+        self._backend.policy_pack(self.desc, ws, bs, self.blob)
+        self._fresh = True
+        return self
+
+    def bind(self, backend):
+        if self._backend is not backend or not self._fresh:
+            self._backend = backend
+            self.refresh()
+        return self
+
+
+def pack_policy(source, device):
+    """PackedPolicy of `source`: """ + POLICY_SOURCES + """.  device: a torch device, or the env that will use the policy."""
+    return PackedPolicy(source, device)
 
 
 CAMERA_MODES = {"track": _lib.CAM_TRACK, "chase": _lib.CAM_CHASE, "fixed": _lib.CAM_FIXED}
@@ -762,6 +881,82 @@ class SteppingStoneVecEnv:
             out = {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
         return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
 
+    def lookahead_policy(self, policy, horizon, env_ids=None, states=None, offsets=None, obs=True, actions=True, final_state=False):
+        """lookahead() with the policy in the loop, in one launch (docs/PHYSICS.md 14): the action of step s of branch k is
+        policy(observation after step s - 1) + offsets[k,s], the observation before step 0 being get_obs() of the env (observe(states[k])
+        with states).  policy: a PackedPolicy (pack_policy), or anything pack_policy takes (packed on every call then).  Branches: [m] ids
+        in env_ids (all N envs in order without), or B per env through offsets [N,B,H,21] / states [N,B,186], every result then [N,B,...].
+        offsets: [m,H,21] float32 or None (zeros) -- exploration noise, a planner's perturbations.  Returns lookahead()'s dict plus "act"
+        [m,H,21] if actions: the actions applied, unclipped; zeros behind a branch's first done.  Given those actions everything else is
+        bit for bit lookahead(act, ...)'s."""
+        if not hasattr(self.backend, "lookahead_policy"):
+            raise NotImplementedError("this backend has no closed-loop look-ahead")
+        horizon = int(horizon)
+        if not 1 <= horizon <= _lib.LOOK_MAX_STEPS:
+            raise ValueError("lookahead_policy: the horizon must lie in [1, %d], got %d" % (_lib.LOOK_MAX_STEPS, horizon))
+        if not isinstance(policy, PackedPolicy):
+            policy = PackedPolicy(policy, self.device)
+        if policy.device != self.device:
+            raise ValueError("lookahead_policy: the policy is packed on %s, the env lives on %s" % (policy.device, self.device))
+        st = None if states is None else self._state_rows(states, "lookahead_policy")
+        off = None
+        if offsets is not None:
+            if not (torch.is_tensor(offsets) or isinstance(offsets, np.ndarray)) or offsets.dtype not in (torch.float32, np.float32):
+                raise ValueError("lookahead_policy: offsets must be a float32 tensor or array")
+            off = torch.as_tensor(offsets).to(self.device).contiguous()
+            if off.dim() not in (3, 4) or tuple(off.shape[-2:]) != (horizon, ACT_DIM):
+                raise ValueError("lookahead_policy: offsets must have shape (m, %d, %d) or (N, B, %d, %d), got %s"
+                                 % (horizon, ACT_DIM, horizon, ACT_DIM, tuple(off.shape)))
+        lead = None
+        if (off is not None and off.dim() == 4) or (st is not None and st.dim() == 3):
+            shape = tuple(off.shape[:2]) if off is not None and off.dim() == 4 else tuple(st.shape[:2])
+            if env_ids is not None or shape[0] != self.num_envs:
+                raise ValueError("lookahead_policy: B branches per env are (%d, B, ...) without env_ids, got %s" % (self.num_envs, shape))
+            if (off is not None and tuple(off.shape[:2]) != shape) or (st is not None and tuple(st.shape[:-1]) != shape):
+                raise ValueError("lookahead_policy: offsets and states must both be (%d, %d, ...)" % shape)
+            lead = (self.num_envs, int(shape[1]))
+            host_ids = np.repeat(np.arange(self.num_envs, dtype=np.int64), lead[1])
+        elif env_ids is None:
+            host_ids = None
+        else:
+            ids = env_ids.detach().cpu().numpy() if torch.is_tensor(env_ids) else np.asarray(env_ids)
+            if ids.size and (ids.ndim > 1 or not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError("env ids must be a one-dimensional sequence of integers, got dtype %s shape %s" % (ids.dtype, ids.shape))
+            host_ids = ids.reshape(-1).astype(np.int64)
+            if host_ids.size and (host_ids.min() < 0 or host_ids.max() >= self.num_envs):
+                raise ValueError("env ids must lie in [0, %d), got %d..%d" % (self.num_envs, host_ids.min(), host_ids.max()))
+        m = self.num_envs if host_ids is None else int(host_ids.size)
+        if st is not None:
+            if st.numel() != m * STATE_DIM or (lead is None and st.dim() != 2):
+                raise ValueError("lookahead_policy: %d branches need states of shape (%d, %d), got %s" % (m, m, STATE_DIM, tuple(st.shape)))
+            st = st.reshape(m, STATE_DIM)
+        if off is not None:
+            if off.numel() != m * horizon * ACT_DIM or (lead is None and off.dim() != 3):
+                raise ValueError("lookahead_policy: %d branches need offsets of shape (%d, %d, %d), got %s"
+                                 % (m, m, horizon, ACT_DIM, tuple(off.shape)))
+            off = off.reshape(m, horizon, ACT_DIM)
+        ids = None if host_ids is None else torch.from_numpy(host_ids.astype(np.int32)).to(self.device)
+        new = lambda *shape: torch.zeros((m,) + shape, dtype=torch.float32, device=self.device)
+        rew = new(horizon)
+        done = torch.ones((m, horizon), dtype=torch.uint8, device=self.device)
+        ob = new(horizon, OBS_DIM) if obs else None
+        ac = new(horizon, ACT_DIM) if actions else None
+        fs = new(STATE_DIM) if final_state else None
+        if m:
+            policy.bind(self.backend)
+            work = torch.empty((m, _lib.LOOK_WORK), dtype=torch.float32, device=self.device)
+            self.backend.lookahead_policy(ids, m, st, horizon, policy.desc, policy.blob, off, ac, ob, rew, done, fs, work)
+        out = {"rew": rew, "done": done.bool(), "ret": rew.sum(1)}
+        if obs:
+            out["obs"] = ob
+        if actions:
+            out["act"] = ac
+        if final_state:
+            out["final_state"] = fs
+        if lead is not None:
+            out = {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
+        return {k: v.cpu().numpy() for k, v in out.items()} if self.return_numpy else out
+
     @property
     def unwrapped(self):
         return self
@@ -1001,6 +1196,19 @@ class SteppingStoneEnv:
             states = self.vec._state_rows(states, "lookahead")
             states = states.reshape(1, STATE_DIM) if states.dim() == 1 else states
         return self.vec.lookahead(a, env_ids=np.zeros(a.shape[0], np.int64), obs=obs, final_state=final_state, states=states)
+
+    def lookahead_policy(self, policy, horizon, states=None, offsets=None, obs=True, actions=True, final_state=False, branches=None):
+        """Closed-loop dry run from the current state (SteppingStoneVecEnv.lookahead_policy): B branches, B the rows of offsets [B,H,21]
+        or of states [B,186] (`branches` without both; default 1) -> the dict with B rows."""
+        if states is not None:
+            states = self.vec._state_rows(states, "lookahead_policy")
+            states = states.reshape(1, STATE_DIM) if states.dim() == 1 else states
+        if offsets is not None:
+            offsets = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets, np.float32)
+            offsets = offsets.reshape((-1,) + offsets.shape[-2:])
+        b = offsets.shape[0] if offsets is not None else (int(states.shape[0]) if states is not None else int(branches or 1))
+        return self.vec.lookahead_policy(policy, horizon, env_ids=np.zeros(b, np.int64), states=states, offsets=offsets, obs=obs,
+                                         actions=actions, final_state=final_state)
 
     def observe(self, states):
         """The observation of packed state rows (SteppingStoneVecEnv.observe): states [m,186] -> [m,60]; one row [186] -> [60]."""
