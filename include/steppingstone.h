@@ -405,7 +405,9 @@ int ss_get_obs_states(ss_env* env, int32_t m, const float* states, float* obs, v
  * NOT bitwise: f itself against another evaluation of the same network (torch, a CPU build of this library's code): the kernel sums each
  * dot product as one f32 fma chain in index order starting from the bias, others sum in other orders; tanh and the division of softsign
  * may differ by a few ulp between implementations.  tests/test_gpu_lookahead_policy.py holds the difference to 8 x the error of a plain
- * f32 evaluation against fp64. */
+ * f32 evaluation against fp64; tests/test_policy_ops.py holds the chain itself (bit for bit for identity / relu networks) and every
+ * output to its own rounding bound.  f is defined for finite activations: an infinite hidden activation gives either the unpadded
+ * network's actions or NaN in every action of the row (docs/PHYSICS.md 14). */
 #define SS_POLICY_MAX_LAYERS 8
 #define SS_POLICY_MAX_WIDTH  256
 enum { SS_POLICY_IDENTITY = 0, SS_POLICY_RELU = 1, SS_POLICY_SOFTSIGN = 2, SS_POLICY_TANH = 3 };

@@ -7,7 +7,8 @@
 // half-broadcast packed multiply(-add) of ss_pair.hpp (tests/test_pair_broadcast.py), the joint-limit and joint-torque forms of
 // ss_dynamics.hpp (tests/test_limit_forms.py) and joint_tau's {leg, arm} pair overload (tests/test_pair_response.py); and the env logic
 // of a control step behind its substeps (ss_kernels.hpp: step_logic on the lane pair, step_score and ep_return_add by value) for
-// tests/test_step_logic.py / tests/np_step_logic.py.
+// tests/test_step_logic.py / tests/np_step_logic.py.  A second entry, ssp_mlp (at the end of the file), runs one MLP phase of the
+// closed-loop look-ahead (ss_policy.hpp) and dumps its activation blocks for tests/test_policy_ops.py / tests/np_policy.py.
 // TEST INFRASTRUCTURE ONLY: never part of libsteppingstone.so, nothing in the package loads it.
 //
 // The same source is compiled two ways:
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "../../steppingstone_amd/csrc/ss_kernels.hpp"
+#include "../../steppingstone_amd/csrc/ss_policy.hpp"
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 #include <atomic>
@@ -1087,6 +1089,82 @@ int run(int op, int n, const float* in, float* out, void* stream) {
   return rc;
 }
 }  // namespace ssp
+
+// ---- the policy MLP of the closed-loop look-ahead (ss_policy.hpp), on its own
+//   int ssp_mlp(const ss_policy_desc* desc, const float* packed, int n, const float* x, float* out, uint32_t prefill_bits, void* stream)
+//     packed: the packed form of desc (ss_policy_words words); x [n][60]; out [(n + 31) / 32][2][256][32]: per group of 32 rows both
+//     activation blocks whole, k-major, as they stand behind one MLP phase.  Every word of the blocks (and, on the device, of the staged
+//     rows) holds prefill_bits before the phase; rows past n are staged as the prefill.  What a dump shows: the last layer's tile (32
+//     columns, 21 of them the action) in block (layers - 1) & 1, the layer before it in the other block, what earlier layers left
+//     behind those, and the prefill wherever the net wrote nothing.
+//     device: one workgroup of kWaves wavefronts per 32 rows over policy::kLdsWords of LDS, as lookahead_policy_kernel has them; every
+//     wavefront calls mlp_phase once.  host: eval_row per row on the same words; its y, t0, t1 laid out the same way (rows past n keep
+//     the prefill).  Returns 0, SSP_BAD_OP for a description that is not valid, or the negative HIP error of the launch.
+#if !defined(SS_PROBE_HOST)
+__global__ __launch_bounds__(ss::kWave * ss::policy::kWaves, 1) void ssp_mlp_kernel(ss::policy::Net net, const float* __restrict__ packed, int n,
+                                                                                    const float* __restrict__ x, float* __restrict__ out,
+                                                                                    uint32_t prefill_bits) {
+  using namespace ss;
+  constexpr int kThreads = kWave * policy::kWaves, kStaged = kEnvsPerWave * SS_OBS_DIM;
+  __shared__ float4 lds4[policy::kLdsWords / 4];
+  float* lds = reinterpret_cast<float*>(lds4);
+  float* xb = lds + kLdsSlots * kWave * 4;
+  const int tid = (int)threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & (kWave - 1);
+  const float fill = ssp::unbits(prefill_bits);
+  const int row0 = (int)blockIdx.x * kEnvsPerWave;
+  // the staged rows where look_row puts them: row r of the group at lds + r * 60
+  for (int i = tid; i < kStaged; i += kThreads) {
+    const int row = row0 + i / SS_OBS_DIM;
+    lds[i] = row < n ? x[(size_t)row0 * SS_OBS_DIM + i] : fill;
+  }
+  for (int i = tid; i < policy::kXWords; i += kThreads) xb[i] = fill;
+#if defined(__HIP_DEVICE_COMPILE__)      // (mlp_phase exists in the device pass only)
+  policy::mlp_phase(net, packed, lds, xb, wave, lane);      // its first barrier stands behind the fills, its last before the dump
+#else
+  (void)wave; (void)lane;
+#endif
+  float* o = out + (size_t)blockIdx.x * policy::kXWords;
+  for (int i = tid; i < policy::kXWords; i += kThreads) o[i] = xb[i];
+}
+#endif
+
+extern "C" int ssp_mlp(const ss_policy_desc* desc, const float* packed, int n, const float* x, float* out, uint32_t prefill_bits,
+                       void* stream) {
+  using namespace ss;
+  policy::Net net;
+  if (!policy::make_net(desc, net) || n < 0 || (n > 0 && (!packed || !x || !out))) return ssp::SSP_BAD_OP;
+  if (n == 0) return 0;
+  const int groups = (n + kEnvsPerWave - 1) / kEnvsPerWave;
+#if defined(SS_PROBE_HOST)
+  (void)stream;
+  const float fill = ssp::unbits(prefill_bits);
+  for (size_t i = 0; i < (size_t)groups * policy::kXWords; ++i) out[i] = fill;
+  for (int row = 0; row < n; ++row) {
+    float y[32], t[2][SS_POLICY_MAX_WIDTH];
+    for (int i = 0; i < 32; ++i) y[i] = fill;
+    for (int b = 0; b < 2; ++b)
+      for (int i = 0; i < SS_POLICY_MAX_WIDTH; ++i) t[b][i] = fill;
+    policy::eval_row(net, packed, x + (size_t)row * SS_OBS_DIM, y, t[0], t[1]);
+    float* o = out + (size_t)(row / kEnvsPerWave) * policy::kXWords + row % kEnvsPerWave;
+    for (int b = 0; b < 2; ++b)
+      for (int i = 0; i < SS_POLICY_MAX_WIDTH; ++i) o[b * policy::kBufWords + i * kEnvsPerWave] = t[b][i];
+    for (int i = 0; i < 32; ++i) o[((net.layers - 1) & 1) * policy::kBufWords + i * kEnvsPerWave] = y[i];      // the tile stands over its block
+  }
+  return 0;
+#else
+  (void)hipGetLastError();
+  ssp_mlp_kernel<<<dim3(groups), dim3(kWave * policy::kWaves), 0, (hipStream_t)stream>>>(net, packed, n, x, out, prefill_bits);
+  return -(int)hipGetLastError();
+#endif
+}
+
+#if defined(SS_PROBE_HOST)
+// the C library's fmaf on n triples (the yardstick of tests/np_policy.py's emulation)
+extern "C" void ssp_fmaf(int n, const float* a, const float* b, const float* c, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = fmaf(a[i], b[i], c[i]);
+}
+#endif
 
 extern "C" int ssp_run(int op, int kind, int n, const float* in, float* out, void* stream) {
   if (n < 0 || (n > 0 && (!in || !out))) return ssp::SSP_BAD_OP;

@@ -3,7 +3,8 @@
   shipped   the reference's shipped actor of the robot (tests/golden/shipped_actor_<kind>.npz): 60 -> 256 x5 -> 21
   ragged    60 -> 37 -> 50 -> 21, softsign / relu / tanh, from a seeded numpy generator: widths that are no multiple of the 32-wide tile,
             scaled so that the tanh outputs stay well inside (-1, 1)
-  linear    60 -> 21, identity: one layer, no activation"""
+  linear    60 -> 21, identity: one layer, no activation
+SHAPES / SHAPE_NAMES: eight more, for tests/test_policy_ops.py and the H = 2 look-aheads (NAMES stays the three above)."""
 import functools
 import os
 
@@ -12,6 +13,22 @@ import numpy as np
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = ("shipped", "ragged", "linear")
 CODE = {"identity": 0, "relu": 1, "softsign": 2, "tanh": 3}
+# The nets of the operator-level tests (tests/test_policy_ops.py) and of the H = 2 look-aheads: shapes the three above do not reach.
+# Weights from a seeded generator with gain 1 / sqrt(K), biases 0.1 sigma: activations stay O(1) at any depth.  Among them every
+# activation stands in a hidden and in the last position.  (Np, Kp: a layer's widths rounded up to the 32-column tile; the kernel
+# walks Kp in groups of 32 with a prefetch one group ahead, and a layer's Np / 32 tiles go round its four wavefronts.)
+_I, _R, _S, _T = "identity", "relu", "softsign", "tanh"
+SHAPES = {
+    "w1": ((60, 1, 21), (_R, _I)),                                        # width 1; Kp = 32: one group, the prefetch re-reads group 0
+    "edge": ((60, 31, 32, 33, 21), (_S, _T, _R, _S)),                     # the tile edge from both sides; groups 1 and 2
+    "deep8": ((60,) + (8,) * 7 + (21,), (_I,) * 8),                       # 8 layers, all identity
+    "wide8": ((60,) + (256,) * 7 + (21,), (_R, _I, _R, _R, _I, _R, _R, _I)),      # 8 layers at full width
+    "t854": ((60, 255, 129, 97, 21), (_T, _S, _R, _T)),                   # tiles 8 / 5 / 4, Kp 256 / 160 / 128
+    "t753": ((60, 224, 160, 96, 21), (_R, _I, _R, _I)),                   # tiles 7 / 5 / 3, an odd number of groups
+    "neck": ((60, 256, 1, 256, 21), (_T, _I, _S, _R)),                    # a wide layer behind a narrow one in the same block
+    "p33": ((60, 33, 21), (_T, _S)),                                      # 2 layers: the action tile in the other block
+}
+SHAPE_NAMES = tuple(SHAPES)
 
 
 @functools.lru_cache(maxsize=None)
@@ -28,6 +45,11 @@ def net(kind, name):
     elif name == "linear":
         g = np.random.default_rng(11)
         out = [((g.standard_normal((21, 60)) * 0.05).astype(np.float32), (g.standard_normal(21) * 0.1).astype(np.float32), "identity")]
+    elif name in SHAPES:
+        widths, acts = SHAPES[name]
+        g = np.random.default_rng(100 + SHAPE_NAMES.index(name))
+        out = [((g.standard_normal((widths[i + 1], widths[i])) / np.sqrt(widths[i])).astype(np.float32),
+                (g.standard_normal(widths[i + 1]) * 0.1).astype(np.float32), acts[i]) for i in range(len(acts))]
     else:
         raise KeyError(name)
     for w, b, _ in out:

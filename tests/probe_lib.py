@@ -1,5 +1,6 @@
 """Builds and binds tests/device/ss_probe.hip: the step kernels' spatial algebra, contact stage, env formulas, one whole substep, the env
-logic of a control step and the forms that must agree bitwise with the ones they replaced, behind one C entry, one operator per call.
+logic of a control step and the forms that must agree bitwise with the ones they replaced, behind one C entry, one operator per call;
+and ssp_mlp, one MLP phase of the closed-loop look-ahead's policy (mlp()).
     host flavour:   compiled here for the CPU (the recipe of native_build.py) into tests/host/libss_probe_host.so, numpy pointers;
     device flavour: steppingstone_amd/lib/libss_probe.so, built for gfx950 by steppingstone_amd.build.build_probe(), torch tensors.
 TEST INFRASTRUCTURE; never imported by steppingstone_amd."""
@@ -38,7 +39,63 @@ def _bind(path):
     lib = C.CDLL(path)
     lib.ssp_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ssp_run.restype = C.c_int
+    lib.ssp_mlp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.ssp_mlp.restype = C.c_int
     return lib
+
+
+MAX_LAYERS, MAX_WIDTH, ROWS = 8, 256, 32
+PREFILL = 0x7FC5A5A5          # a quiet NaN with a payload of its own: a stale word that is read turns up as a NaN, one left alone as these bits
+
+
+class PolicyDesc(C.Structure):          # ss_policy_desc (include/steppingstone.h)
+    _fields_ = [("layers", C.c_int32), ("width", C.c_int32 * (MAX_LAYERS + 1)), ("activation", C.c_int32 * MAX_LAYERS)]
+
+
+def mlp(flavour, widths, codes, packed, x, prefill=PREFILL):
+    """ssp_mlp: one MLP phase of the net (widths [layers + 1], activation codes [layers]) over the packed words `packed` on the rows
+    x [n,60] -> the two activation blocks by row, uint32 bit patterns [32 * groups, 2, 256] (rows past n included: on the device they
+    were staged as the prefill)."""
+    lib = load(flavour)
+    d = PolicyDesc()
+    d.layers = len(codes)
+    for i, w in enumerate(widths):
+        d.width[i] = int(w)
+    for i, a in enumerate(codes):
+        d.activation[i] = int(a)
+    x = np.ascontiguousarray(x, np.float32)
+    packed = np.ascontiguousarray(packed, np.float32)
+    n = x.shape[0]
+    assert x.shape == (n, 60) and n > 0
+    groups = (n + ROWS - 1) // ROWS
+    words = groups * 2 * MAX_WIDTH * ROWS
+    if flavour == "host":
+        out = np.zeros(words, np.float32)
+        rc = lib.ssp_mlp(C.byref(d), packed.ctypes.data_as(C.c_void_p), n, x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                         prefill, None)
+    else:
+        import torch
+        up = lambda a: torch.from_numpy(a.view(np.int32).copy()).to("cuda:0").contiguous()
+        d_p, d_x = up(packed), up(x)
+        d_out = torch.zeros(words, dtype=torch.int32, device="cuda:0")
+        stream = torch.cuda.current_stream(d_x.device)
+        rc = lib.ssp_mlp(C.byref(d), C.c_void_p(d_p.data_ptr()), n, C.c_void_p(d_x.data_ptr()), C.c_void_p(d_out.data_ptr()), prefill,
+                         C.c_void_p(stream.cuda_stream))
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+    assert rc == 0, "ssp_mlp returned %d" % rc
+    return np.ascontiguousarray(out.view(np.uint32).reshape(groups, 2, MAX_WIDTH, ROWS).transpose(0, 3, 1, 2)).reshape(groups * ROWS, 2, MAX_WIDTH)
+
+
+def c_fmaf(a, b, c):
+    """the C library's fmaf, elementwise (host build)"""
+    lib = load("host")
+    a, b, c = (np.ascontiguousarray(v, np.float32) for v in (a, b, c))
+    out = np.empty_like(a)
+    lib.ssp_fmaf.argtypes = [C.c_int] + [C.c_void_p] * 4
+    lib.ssp_fmaf.restype = None
+    lib.ssp_fmaf(a.size, *[v.ctypes.data_as(C.c_void_p) for v in (a, b, c, out)])
+    return out
 
 
 _libs = {}

@@ -9,7 +9,11 @@ tests/lookahead_cases.py on N = 70 envs (three workgroups of 32 rows, the last w
      or the horizon; the env is untouched (its 186 words, its next real step); the row of a bad id and the words behind every buffer
      are never written
   5  one graph capture of pack + call, replayed after the weights changed in place, gives the uncaptured result
-  6  the Python surface: pack_policy from each kind of source, the [N,B] forms, numpy mode, the single-env wrapper; the C API's refusals"""
+  6  the Python surface: pack_policy from each kind of source, the [N,B] forms, numpy mode, the single-env wrapper; the C API's refusals
+  7  the nets of policy_nets.SHAPES (the shapes tests/test_policy_ops.py pins on their own) through the whole call, H = 2, so that the
+     second MLP phase runs over the blocks the first one left: closed loop equals open loop, every action within its own fp64 bound
+     (tests/np_policy.py), and for the identity / relu nets bit for bit the exact fma chain (which tests/test_lookahead_policy.py
+     holds equal to the host build's policy_eval)"""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +21,7 @@ import pytest
 import torch
 
 import lookahead_cases as lc
+import np_policy as npp
 import policy_nets as pn
 
 pytestmark = pytest.mark.gpu
@@ -92,6 +97,34 @@ def test_closed_loop_is_the_open_loop_under_the_policys_actions(kind, name):
             assert int(alive.sum()) >= LIVE_FLOOR, "the closed loop lost its live rows"
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize("name", pn.SHAPE_NAMES)
+@pytest.mark.parametrize("kind", lc.KINDS)
+def test_two_steps_under_the_shape_nets(kind, name):
+    """For the identity / relu nets the actions are compared, bit for bit, with np_policy.chain instead of the host build's
+    lhp.policy_eval, so that no host code is compiled on the GPU machine: the chain is numpy's emulation of fmaf, held to the C
+    library's on 1.4 million triples, and tests/test_lookahead_policy.py and tests/test_policy_ops.py hold policy_eval / eval_row
+    equal to it."""
+    from steppingstone_amd.envs import pack_policy
+    e = _env(kind, N)
+    e.set_state(_states(kind))
+    layers = pn.net(kind, name)
+    got = e.lookahead_policy(pack_policy(layers, e), 2, final_state=True)
+    assert torch.isfinite(got["act"]).all()
+    _assert_same(got, e.lookahead(got["act"], final_state=True), "%s %s, H = 2" % (kind, name))
+    inputs = torch.cat([e.get_obs()[:, None], got["obs"][:, :-1]], 1).cpu().numpy()
+    acts, live = got["act"].cpu().numpy(), _live_steps(got["done"])
+    assert live[:, 0].all() and live[:, 1].sum() >= 35, "the second step needs live rows"
+    for s in range(2):
+        x, act = inputs[live[:, s], s], acts[live[:, s], s]
+        y, err = npp.eval64(layers, x, npp.TANH_ULPS["device"])[-1]
+        d = np.abs(act.astype(np.float64) - y)
+        print("GPU %s %s step %d: worst err / bound %.3f over %d rows" % (kind, name, s, (d / err).max(), x.shape[0]))
+        assert (d <= err).all(), "%s %s: step %d, rows %s outside their bounds" % (kind, name, s, np.nonzero(~(d <= err).all(1))[0][:8].tolist())
+        if npp.is_chain_net(layers):
+            assert npp.same_bits(act, npp.chain(layers, x)[-1]).all(), "%s %s: step %d is not the exact chain" % (kind, name, s)
+    e.close()
 
 
 @pytest.mark.parametrize("kind", lc.KINDS)

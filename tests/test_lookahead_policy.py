@@ -9,6 +9,9 @@ tests/lookahead_cases.py under the three networks of tests/policy_nets.py.
   4  a row's bits do not depend on m, its position, repeated ids, the outputs asked for or the horizon
   5  ss_policy_words on valid and invalid descriptions, the refusals of the C functions that can be had without a GPU
   6  the stand-alone AddressSanitizer / UBSan program on the 64 cases with the ragged net
+  7  the nets of policy_nets.SHAPES (the shapes tests/test_policy_ops.py pins on their own) through the whole call: N = 70, H = 2, so that
+     the second MLP phase runs over the blocks the first one left; closed loop equals open loop, every action within its own fp64
+     bound (tests/np_policy.py), and for the identity / relu nets bit for bit the exact fma chain and policy_eval
 The shipped actors keep most walking rows alive (39 of 40 Walker3D, 36 of 40 Mike in the host build; all 24 fall rows): LIVE_FLOOR keeps
 the per-step comparisons from passing on frozen rows."""
 import ctypes as C
@@ -23,6 +26,7 @@ import lookahead_host_lib as lh
 import lookahead_policy_host_lib as lhp
 import lookahead_states_host_lib as lhs
 import native_build
+import np_policy as npp
 import policy_nets as pn
 
 pytestmark = pytest.mark.skipif(not native_build.hipcc(), reason="needs hipcc")
@@ -157,6 +161,27 @@ def test_a_rows_bits_are_its_own(kind):
     cut = 8
     head = lhp.lookahead_policy(k, st, net, cut, offsets=np.ascontiguousarray(off[:, :cut]), **KW)
     same(head, {n: full[n][:, :cut] for n in ("obs", "rew", "done", "act")}, keys=("obs", "rew", "done", "act"), what="%s: prefix" % kind)
+
+
+@pytest.mark.parametrize("name", pn.SHAPE_NAMES)
+@pytest.mark.parametrize("kind", lc.KINDS)
+def test_two_steps_under_the_shape_nets(kind, name):
+    k, st = lc.KINDS.index(kind), lc.tile(kind, 70)[0]
+    layers = pn.net(kind, name)
+    got = lhp.lookahead_policy(k, st, layers, 2, fill=-777.25, **KW)
+    assert got["tails_ok"] and np.isfinite(got["act"]).all()
+    same(got, lh.lookahead(k, st, got["act"], **KW), what="%s %s, H = 2" % (kind, name))
+    inputs = np.concatenate([lhs.get_obs(k, st)[:, None], got["obs"][:, :-1]], 1)
+    live = live_steps(got["done"])
+    assert live[:, 0].all() and live[:, 1].sum() >= 35, "the second step needs live rows"
+    for s in range(2):
+        x, act = inputs[live[:, s], s], got["act"][live[:, s], s]
+        y, err = npp.eval64(layers, x, npp.TANH_ULPS["host"])[-1]
+        d = np.abs(act.astype(np.float64) - y)
+        print("%s %s step %d: worst err / bound %.3f over %d rows" % (kind, name, s, (d / err).max(), x.shape[0]))
+        assert (d <= err).all(), "%s %s: step %d, rows %s outside their bounds" % (kind, name, s, np.nonzero(~(d <= err).all(1))[0][:8].tolist())
+        if npp.is_chain_net(layers):
+            assert npp.same_bits(act, npp.chain(layers, x)[-1]).all() and npp.same_bits(act, lhp.policy_eval(layers, x)).all()
 
 
 def desc(widths, acts=None):
